@@ -442,7 +442,40 @@ def build_parser():
     ap.add_argument("--no-also", action="store_true",
                     help="the default N=1 run measures the other BASELINE configurations in the same process after the headline "
                          "(`also`: configs[2] 128^3 bf16, configs[4] both readings at batch 16, the fp32x mode); this skips them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step of the headline configuration handed its caller "
+                         "as DIR/<name>.npy (rank 0): see dump_outputs.  The inputs and parameters are seeded, so the same "
+                         "arguments give the same inputs and two builds can be compared output for output")
     return ap
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, outputs, net):
+    """Write what a train step (or val_step) hands its caller as out_dir/<name>.npy: `loss`, the model's outputs (`logits`,
+    `d_mri`, `d_pet`), every parameter after the optimizer step (`param.<name>`), its gradient from that step (`grad.<name>`)
+    and the buffers (`buffer.<name>`).  float32, float64 for integer tensors (BatchNorm step counters).  model_ad's 4.2 M
+    parameters make ~32 MB with their gradients; a dump above DUMP_LIMIT_BYTES is refused.  Returns the bytes written."""
+    import numpy as np
+    arrays = {"loss": loss, **outputs}
+    for k, p in net.named_parameters():
+        arrays[f"param.{k}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{k}"] = p.grad
+    for k, b in net.named_buffers():
+        arrays[f"buffer.{k}"] = b
+    host = {}
+    for k, t in arrays.items():
+        t = t.detach().cpu()
+        host[k] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
 
 
 # The other BASELINE.json configurations, measured in the SAME process after the headline when bench.py runs with its
@@ -502,6 +535,8 @@ def self_launch(args, argv):
 def main():
     import copy
     args = build_parser().parse_args()
+    if args.dump_outputs and (args.steps < 1 or args.roofline_only):
+        raise SystemExit("--dump-outputs needs at least one timed step (--steps >= 1, no --roofline-only)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
     from transmf_ad_amd.parallel import init_from_env
@@ -625,12 +660,19 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
         h2d_gbps = 5 * pin.numel() * 4 / (time.perf_counter() - t_h) / 1e9
         del pin, dbuf
 
+    # the model's outputs of the latest step (--dump-outputs); holding them keeps nothing alive that the step's returned loss
+    # does not already keep until the next step
+    last = {}
+
     def val_step():
         net.eval()
         with torch.no_grad():
             if args.model == "single":
-                return crit(net(mri), label)
-            lo, _dm, _dp = net(mri, pet)
+                lo = net(mri)
+                last["logits"] = lo
+                return crit(lo, label)
+            lo, dm, dp = net(mri, pet)
+            last.update(logits=lo, d_mri=dm, d_pet=dp)
             return crit(lo, label)
 
     def step():
@@ -644,9 +686,12 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
             mri, pet, label = mri0, pet0, label0
         opt.zero_grad()
         if args.model == "single":          # kfold_train_single.py:91-113: plain CE on model_single(MRI)
-            loss = crit(net(mri), label)
+            lo = net(mri)
+            last["logits"] = lo
+            loss = crit(lo, label)
         else:
             lo, dm, dp = net(mri, pet)
+            last.update(logits=lo, d_mri=dm, d_pet=dp)
             ce_loss = crit(lo, label)
             ad_loss = (crit(dm, ones) + crit(dp, zeros)) / 2
             if not args.no_item_sync:       # the reference reads both losses on the host BEFORE backward
@@ -767,6 +812,8 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
 
     ms_per_step = dt / max(args.steps, 1) * 1e3
     pairs_per_s = world * B * args.steps / dt
+    if args.dump_outputs and not brief and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last, net.module if hasattr(net, "module") else net)
     # the timed region is over: give this configuration's memory back before the roofline / CPU legs and the next record
     del net, opt
     torch.cuda.empty_cache()

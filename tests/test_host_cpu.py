@@ -458,3 +458,39 @@ def test_bench_launches_its_own_ranks():
     r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env2, capture_output=True,
                         text=True, timeout=300)
     assert r2.returncode != 0 and "--nproc-per-node must equal --gpus" in r2.stderr
+
+
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs): the loss, the model's outputs, the parameters after the optimizer
+    step, their gradients and the buffers, one float32 file each (float64 for integer buffers), equal to the tensors the step
+    left; without a timed step there is nothing to dump and the option is refused before any device call."""
+    import subprocess
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(6, 4), torch.nn.BatchNorm1d(4), torch.nn.Linear(4, 2))
+    net[2].bias.requires_grad_(False)                 # a parameter without a gradient gets no grad.* file
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    lo = net(torch.rand(5, 6))
+    loss = torch.nn.functional.cross_entropy(lo, torch.arange(5) % 2)
+    loss.backward()
+    opt.step()
+    n = bench.dump_outputs(str(tmp_path / "d"), loss, {"logits": lo.detach()}, net)
+    files = sorted(os.listdir(tmp_path / "d"))
+    want = (["loss.npy", "logits.npy"] + [f"param.{k}.npy" for k, _ in net.named_parameters()]
+            + [f"grad.{k}.npy" for k, p in net.named_parameters() if p.grad is not None]
+            + [f"buffer.{k}.npy" for k, _ in net.named_buffers()])
+    assert files == sorted(want) and "grad.2.bias.npy" not in files
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in files}
+    assert n == sum(a.nbytes for a in got.values())
+    assert got["loss"].dtype == np.float32 and got["loss"] == np.float32(loss.item())
+    assert np.array_equal(got["logits"], lo.detach().numpy()) and got["logits"].dtype == np.float32
+    assert np.array_equal(got["param.0.weight"], net[0].weight.detach().numpy())
+    assert np.array_equal(got["grad.0.weight"], net[0].weight.grad.numpy())
+    assert got["buffer.1.num_batches_tracked"].dtype == np.float64 and got["buffer.1.num_batches_tracked"] == 1.0
+    assert np.array_equal(got["buffer.1.running_var"], net[1].running_var.numpy())
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dump-outputs", str(tmp_path / "e")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--dump-outputs needs at least one timed step" in r.stderr
+    assert not os.path.exists(tmp_path / "e")
