@@ -168,6 +168,10 @@ int    tmf_conv_wino_mode(void);
  * bricks of one sample and 4x4x4 bricks of four samples — tmf_conv3d_wino_bricks() follows it); 0: the two-waves-per-
  * SIMD kernels of round 4.  Same results up to fp32 rounding of the output transform's order of additions. */
 int    tmf_wino_p_mode(void);
+/* tmf_set_option("wino_cus", n) — a test and experiment aid: n > 0 caps the workgroups of the persistent Winograd forward / data-
+ * gradient kernels at min(n, compute units), so that every workgroup walks many items and launches split into windows of
+ * n x (item table) items; 0 (default) returns to the device's count (or TMF_WINO_CUS).  Process-wide.  tmf_conv3d_wino_stat_blocks
+ * follows it: a statistics buffer sized under one setting must not be launched under a larger one. */
 /* Weight gradient in the same form: dU_p = V_p^T Z_p per position of the transformed tile (V = the forward's input transform of
  * x, Z = A dz A^T), summed over all tiles on the fp32 matrix pipe, then dw = G^T dU G (fp64) — replaces the weight gradient of
  * convolution_backward at networks.py:28,31,37,40,46 for cin % 32 == 0 and cout % 32 == 0.  Arguments as tmf_conv3d_wgrad. */

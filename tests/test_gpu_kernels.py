@@ -1290,7 +1290,7 @@ WINOX_SHAPES = [
     (1, 4, 8, 8, 32, 32),           # one brick, one item per workgroup
     (2, 7, 9, 13, 32, 32),          # every brick ragged
     (1, 8, 16, 16, 32, 64),         # two groups of output channels
-    (2, 12, 24, 24, 64, 128),       # four chunks, four groups: workgroups walk several items and groups
+    (2, 12, 24, 24, 64, 128),       # four chunks, four groups (216 items: ONE per workgroup on 256 CUs; many per workgroup in test_winograd_capped_grid)
     (2, 9, 17, 21, 128, 64),        # eight chunks, odd edges
     (5, 16, 16, 24, 32, 32),        # more items than compute units on a small device are still a strided list
     # round 6: volumes whose items lie better with the 4-voxel side along h — the kernel then runs TRANSPOSED (its d axis = the
@@ -1454,6 +1454,264 @@ def test_conv3d_winograd_eval_block_in_one_pass(shape, pool):
     if pool:
         ref = F.max_pool3d(ref, 2, 2)
     assert _relerr(_ncdhw(y.cpu()), ref) < 3e-6
+
+
+@pytest.fixture(params=[1, 7, 16], ids=["cus1", "cus7", "cus16"])
+def wino_cus(request):
+    """Run a raw-op test with the persistent Winograd kernels capped at n workgroups (tmf_set_option("wino_cus", n)): every
+    workgroup walks many items, and a launch splits into windows of n x (item table) items.  1: one workgroup takes every item;
+    7: divides no 3- or 5-group cout (the split kernel's workgroups change channel group from item to item); 16: the XCD remap
+    of the item order.  Raw ops only — a model's buffers are sized under the setting they were planned with."""
+    from transmf_ad_amd import _lib
+    _lib.call("tmf_set_option", b"wino_cus", request.param)
+    try:
+        yield request.param
+    finally:
+        _lib.call("tmf_set_option", b"wino_cus", 0)
+
+
+def _wino_tab(kernel):
+    """item-table entries per workgroup (= items per workgroup and launch) of a persistent Winograd forward kernel"""
+    if kernel.startswith("conv3d_winox_kernel"):
+        return 256
+    return 448 if kernel.endswith(", 1>") else 768         # conv3d_wino_p_kernel<MODE, GEOM>: PGeom<GEOM>::TAB
+
+
+def _wino_first_grid(items, ncu, tab):
+    """workgroups of a launch's first window (tmf_winox_launch / launch_wino_p_g): min(n, ncu), evened to the rounds it needs"""
+    n = min(items, ncu * tab)
+    if n <= ncu:
+        return n
+    rounds = -(-n // ncu)
+    return -(-n // rounds)
+
+
+def _wino_items(B, D, H, W, cin, cout):
+    from transmf_ad_amd import _lib
+    return _lib.query("tmf_conv3d_wino_bricks2", B, D, H, W, cin, cout) * (cout // 32)
+
+
+def _wino_fwd_stats(xg, uf, cin, cout):
+    """tmf_conv3d_fwd_wino through the C ABI into NaN-prefilled z and statistics ((tmf_conv3d_wino_stat_blocks, 2, cout))"""
+    from transmf_ad_amd import _lib
+    B, D, H, W = xg.shape[:4]
+    rows = _lib.query("tmf_conv3d_wino_stat_blocks", B, D, H, W)
+    z = torch.full((B, D, H, W, cout), float("nan"), device=DEV)
+    part = torch.full((rows, 2, cout), float("nan"), device=DEV)
+    _lib.call("tmf_conv3d_fwd_wino", xg.data_ptr(), uf.data_ptr(), z.data_ptr(), part.data_ptr(), B, D, H, W, cin, cout, _ops()._stream())
+    return z, part
+
+
+def _wino_eval_block(xg, uf, scg, shg, cin, cout, pool):
+    from transmf_ad_amd import _lib
+    B, D, H, W = xg.shape[:4]
+    y = torch.full((B, D // 2, H // 2, W // 2, cout) if pool else (B, D, H, W, cout), float("nan"), device=DEV)
+    _lib.call("tmf_conv3d_fwd_wino_affine", xg.data_ptr(), uf.data_ptr(), scg.data_ptr(), shg.data_ptr(), y.data_ptr(),
+              B, D, H, W, cin, cout, _lib.pool_code(pool), 0.01, _ops()._stream())
+    return y
+
+
+CAPPED_CASES = [
+    # (B, D, H, W, cin, cout), wino_x, forward kernel, what the case is there for (asserted in the test):
+    #   windows  more items than one window at cap 1 (later windows add into the rows: stat_accum)
+    #   cout3/5, cin3/5  3 or 5 channel groups in the forward (statistics) / in the data gradient
+    #   transposed  the split kernel's d axis is the tensor's h axis;  short  a last group of fewer than 4 samples
+    #   flush7  at cap 7 the split kernel's workgroups change channel group with every item (statistics flush, affine reload)
+    #   remap16  the first window's grid at cap 16 is a multiple of 8 (the XCD remap of the item order)
+    ((2, 12, 24, 24, 32, 160), 1, "conv3d_winox_kernel<1>", "windows cout5 flush7 remap16"),
+    ((1, 4, 16, 56, 160, 96), 1, "conv3d_winox_kernel<1>", "cout3 cin5 flush7"),
+    ((2, 7, 9, 13, 96, 64), 1, "conv3d_winox_kernel<1>", "cin3"),                   # every brick ragged
+    ((2, 12, 24, 24, 64, 128), 1, "conv3d_winox_kernel<1>", "remap16"),
+    ((2, 22, 27, 22, 64, 64), 1, "conv3d_winox_kernel<1>", "transposed remap16"),
+    ((2, 24, 32, 32, 8, 160), 1, "conv3d_wino_p_kernel<1, 0>", "windows cout5 remap16"),
+    ((7, 11, 13, 11, 16, 32), 1, "conv3d_wino_p_kernel<1, 1>", "short"),
+    ((8, 12, 12, 16, 8, 256), 1, "conv3d_wino_p_kernel<1, 1>", "windows remap16"),
+    ((1, 4, 16, 56, 160, 96), 0, "conv3d_wino_p_kernel<1, 0>", "cout3 cin5"),
+]
+_CAPPED_BASE = {}
+
+
+def _capped_outputs(xg, uf, ud, dzg, scg, shg, cin, cout):
+    z, part = _wino_fwd_stats(xg, uf, cin, cout)
+    z2, part2 = _wino_fwd_stats(xg, uf, cin, cout)
+    out = {"z": z, "part": part, "z2": z2, "part2": part2}
+    if ud is not None:
+        out["dx"], _, _ = _ops().conv3d_wino_raw(dzg, ud, cout, cin, False)
+    for pool in (None, "max"):
+        out[f"y_{pool}"] = _wino_eval_block(xg, uf, scg, shg, cin, cout, pool)
+        out[f"y2_{pool}"] = _wino_eval_block(xg, uf, scg, shg, cin, cout, pool)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("case", CAPPED_CASES, ids=lambda c: "x{}-{}".format(c[1], "x".join(map(str, c[0]))))
+def test_winograd_capped_grid(case, wino_cus):
+    """The persistent Winograd kernels (conv3d_winox_kernel<0..3>, conv3d_wino_p_kernel<*, 0 | 1>) with their workgroups capped
+    (tmf_set_option("wino_cus", n)), so that every workgroup walks a strided list of items: the cross-item prefetch of halo and
+    weights, the statistics flush where the channel group changes, the affine reload per group, windows beyond the item table and
+    the XCD remap all run.  An item's arithmetic belongs to its workgroup alone: z, dx and the eval block are BIT-identical to the
+    uncapped launch; each holds its fp64 bound; the statistic rows (C ABI, NaN-prefilled) are finite, exactly 0 at and past the
+    first window's grid, and sum to z's fp64 sums; every output repeats bit for bit."""
+    from transmf_ad_amd import _lib
+    ops = _ops()
+    shape, xmode, kernel, tags = case
+    B, D, H, W, cin, cout = shape
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    _lib.call("tmf_set_option", b"wino_x", xmode)
+    try:
+        names = [_lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cin, cout, 1),
+                 _lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cout, cin, 0)]
+        assert names[0].decode() == kernel
+        tab = _wino_tab(kernel)
+        items = _wino_items(B, D, H, W, cin, cout)
+        want_d = ops.wino_ok(cout, cin)
+        # what the case is there for
+        for t in tags.split():
+            if t == "windows":
+                assert items > tab                                             # more than one window at cap 1
+            elif t in ("cout3", "cout5", "cin3", "cin5"):
+                n = int(t[-1])
+                assert (cout if t[1] == "o" else cin) == 32 * n and (t[1] == "o" or want_d)
+            elif t == "transposed":
+                assert -(-H // 4) * -(-D // 8) < -(-D // 4) * -(-H // 8)
+            elif t == "short":
+                assert B % 4 != 0 and tab == 448
+            elif t == "flush7":                                                # (the channel group is the split kernel's fast index)
+                assert tab == 256 and _wino_first_grid(items, 7, tab) % (cout // 32) != 0
+            else:
+                assert t == "remap16" and _wino_first_grid(items, 16, tab) % 8 == 0
+        if shape + (xmode,) not in _CAPPED_BASE:                               # inputs, fp64 references, the uncapped launch
+            x = _rand(B, cin, D, H, W, seed=341)
+            w = _rand(cout, cin, 3, 3, 3, seed=342, scale=(cin * 27) ** -0.5)
+            dz = _rand(B, cout, D, H, W, seed=343)
+            sc, sh = 1 + _rand(cout, seed=344, scale=0.2), _rand(cout, seed=345, scale=0.2)
+            g = {"xg": _ndhwc(x).to(DEV), "dzg": _ndhwc(dz).to(DEV), "scg": sc.to(DEV), "shg": sh.to(DEV)}
+            g["uf"], g["ud"] = ops.pack_weights_wino(w.to(DEV), True, want_d)
+            ref = {"z": F.conv3d(x.double(), w.double(), None, 1, 1)}
+            if want_d:
+                ref["dx"] = F.conv_transpose3d(dz.double(), w.double(), None, 1, 1)
+            ref["y_None"] = F.leaky_relu(ref["z"] * sc.double().view(1, -1, 1, 1, 1) + sh.double().view(1, -1, 1, 1, 1), 0.01)
+            ref["y_max"] = F.max_pool3d(ref["y_None"], 2, 2)
+            _lib.call("tmf_set_option", b"wino_cus", 0)
+            try:
+                base = _capped_outputs(g["xg"], g["uf"], g["ud"], g["dzg"], g["scg"], g["shg"], cin, cout)
+                base_names = [_lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cin, cout, 1),
+                              _lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cout, cin, 0)]
+            finally:
+                _lib.call("tmf_set_option", b"wino_cus", wino_cus)
+            _CAPPED_BASE[shape + (xmode,)] = g, ref, base, base_names
+        g, ref, base, base_names = _CAPPED_BASE[shape + (xmode,)]
+        assert names == base_names
+        got = _capped_outputs(g["xg"], g["uf"], g["ud"], g["dzg"], g["scg"], g["shg"], cin, cout)
+    finally:
+        _lib.call("tmf_set_option", b"wino_x", 1)
+    cap = min(wino_cus, ncu)
+    for res, n_cu in ((got, cap), (base, ncu)):
+        # bitwise repeatable, and the capped grid computes the uncapped grid's bits
+        for k in ("z", "part", "y_None", "y_max"):
+            k2 = k.replace("_", "2_") if k.startswith("y") else k + "2"
+            assert torch.equal(res[k], res[k2]), (k, n_cu)
+        for k in ("z", "dx", "y_None", "y_max"):
+            if k in res:
+                assert torch.equal(res[k], base[k]), (k, n_cu)
+                assert _relerr(_ncdhw(res[k].cpu()), ref[k]) < (3e-6 if k.startswith("y") else 2e-6), (k, n_cu)
+        # statistics: one row per workgroup; rows at and past the first window's grid are zeros, none is left unwritten
+        part = res["part"].double().cpu()
+        grid = _wino_first_grid(items, n_cu, tab)
+        assert part.shape == (n_cu, 2, cout) and bool(torch.isfinite(part).all())
+        assert bool((part[grid:] == 0).all()), (grid, n_cu)
+        s1, s2 = part[:, 0].sum(0), part[:, 1].sum(0)
+        zz = res["z"].double().cpu()
+        assert (s1 - zz.sum((0, 1, 2, 3))).abs().max().item() <= 2e-6 * zz.abs().sum((0, 1, 2, 3)).max().item(), n_cu
+        assert _relerr(s2, (zz ** 2).sum((0, 1, 2, 3))) < 2e-6, n_cu
+
+
+WINO_FULL_LAYERS = [
+    # (B, D, H, W, cin, cout), forward kernel, crops of z / dx (sample, d0, h0, w0) of size `size` (clipped to the volume): the two
+    # corners (the far one holds the last sample and the ragged last brick), bricks seams straddled on every axis
+    ((8, 48, 48, 48, 32, 64), "conv3d_winox_kernel<1>", (6, 10, 10),         # conv2.3 at BASELINE size: 6 912 items
+     [(0, 0, 0, 0), (7, 42, 38, 38), (3, 10, 14, 22), (7, 18, 30, 6)]),
+    ((8, 12, 12, 12, 128, 256), "conv3d_wino_p_kernel<1, 1>", (6, 6, 6),     # conv4.0: four samples x 4x4x4 bricks, 432 items
+     [(0, 0, 0, 0), (7, 6, 6, 6), (4, 3, 3, 3), (3, 1, 5, 2)]),
+    ((2, 45, 54, 45, 32, 64), "conv3d_winox_kernel<1>", (6, 10, 10),         # ADNI 91x109x91, first pooled level: ragged on every axis
+     [(0, 0, 0, 0), (1, 39, 44, 35), (0, 18, 22, 14), (0, 37, 3, 33)]),
+    ((2, 22, 27, 22, 64, 64), "conv3d_winox_kernel<1>", (10, 6, 10),         # ... two levels down: transposed items (4 voxels along h)
+     [(0, 0, 0, 0), (1, 12, 21, 12), (0, 3, 6, 5), (1, 11, 13, 11)]),
+]
+
+
+def _conv_crop_ref(vp, w, b, o, size):
+    """fp64 3x3x3 convolution of one crop of the output: the crop's window of the zero-padded NDHWC input vp, no padding"""
+    sl = tuple(slice(o[i], o[i] + size[i] + 2) for i in range(3))
+    v = vp[(b,) + sl].double().cpu().permute(3, 0, 1, 2).unsqueeze(0)
+    return F.conv3d(v, w.double().cpu())[0].permute(1, 2, 3, 0)
+
+
+@pytest.mark.parametrize("layer", WINO_FULL_LAYERS, ids=lambda l: "x".join(map(str, l[0])))
+def test_full_size_winograd_conv_properties(layer):
+    """The default Winograd kernels at full size, default grid (the twin of test_full_size_conv_properties): (i) exact power-of-
+    two homogeneity of forward, statistics (x 4 / x 16), data and weight gradient — the exact bf16 splits and the fp64 filter
+    transform commute with a scale by 4; (ii) adjointness <dz, conv(x, w)> == <wgrad(x, dz), w> == <dgrad(dz, w), x>; (iii) crops
+    of z and dx against fp64 torch on the padded input window: corners, brick seams, the ragged last brick, the last sample."""
+    from transmf_ad_amd import _lib
+    ops = _ops()
+    (B, D, H, W, cin, cout), kernel, size, crops = layer
+    assert _lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cin, cout, 1).decode() == kernel
+    assert _lib.query("tmf_conv3d_wino_kernel_name2", B, D, H, W, cout, cin, 0).decode() == kernel.replace("<1", "<0")
+    if (H, W) == (27, 22):
+        assert -(-H // 4) * -(-D // 8) < -(-D // 4) * -(-H // 8)             # (the transposed orientation)
+    g = torch.Generator(device=DEV).manual_seed(17)
+    x = torch.randn((B, D, H, W, cin), device=DEV, generator=g)
+    dz = torch.randn((B, D, H, W, cout), device=DEV, generator=g)
+    w = torch.randn((cout, cin, 3, 3, 3), device=DEV, generator=g) * (27 * cin) ** -0.5
+    uf, ud = ops.pack_weights_wino(w, True, True)
+    z, part, _ = ops.conv3d_wino_raw(x, uf, cin, cout, True)
+    z4, part4, _ = ops.conv3d_wino_raw(x * 4.0, uf, cin, cout, True)
+    assert torch.equal(z4, z * 4.0)
+    assert torch.equal(part4[:, 0], part[:, 0] * 4.0) and torch.equal(part4[:, 1], part[:, 1] * 16.0)
+    zs = z.double().sum(dim=(0, 1, 2, 3))
+    assert (part[:, 0].double().sum(0) - zs).abs().max().item() <= 2e-6 * z.double().abs().sum(dim=(0, 1, 2, 3)).max().item()
+    assert _relerr(part[:, 1].double().sum(0), (z.double() ** 2).sum(dim=(0, 1, 2, 3)).cpu()) < 2e-6
+    dx, _, _ = ops.conv3d_wino_raw(dz, ud, cout, cin, False)
+    dx4, _, _ = ops.conv3d_wino_raw(dz * 4.0, ud, cout, cin, False)
+    assert torch.equal(dx4, dx * 4.0)
+    dw = ops.conv3d_wgrad_wino(x, dz, cin, cout, reference_layout=True)
+    dw4 = ops.conv3d_wgrad_wino(x * 4.0, dz, cin, cout, reference_layout=True)
+    assert torch.equal(dw4, dw * 4.0)
+    a = (dz.double() * z.double()).sum().item()
+    b = (dw.double() * w.double()).sum().item()
+    c = (dx.double() * x.double()).sum().item()
+    scale = (dz.double().abs() * z.double().abs()).sum().item()
+    assert abs(a - b) <= 1e-6 * scale and abs(a - c) <= 1e-6 * scale, (a, b, c, scale)
+    xp = F.pad(x, (0, 0, 1, 1, 1, 1, 1, 1))
+    dzp = F.pad(dz, (0, 0, 1, 1, 1, 1, 1, 1))
+    wt = w.flip(2, 3, 4).transpose(0, 1)                                      # the data gradient as a convolution
+    for b_, d0, h0, w0 in crops:
+        o = (d0, h0, w0)
+        assert all(0 <= o[i] and o[i] + size[i] <= (D, H, W)[i] for i in range(3)) and 0 <= b_ < B
+        sl = (b_,) + tuple(slice(o[i], o[i] + size[i]) for i in range(3))
+        assert _relerr(z[sl], _conv_crop_ref(xp, w, b_, o, size)) < 2e-6, (b_, o)
+        assert _relerr(dx[sl], _conv_crop_ref(dzp, wt, b_, o, size)) < 2e-6, (b_, o)
+
+
+def test_full_size_winograd_eval_block_is_the_two_kernel_sequence():
+    """The one-pass eval block (conv3d_winox_kernel<3>: conv, folded BatchNorm, LeakyReLU, 2x2x2 max pool) at full size, 8 x 48^3,
+    32 -> 64, default grid: bitwise the Winograd conv followed by tmf_bn_act_pool_fwd_t."""
+    from transmf_ad_amd import _lib
+    ops = _ops()
+    B, S, cin, cout = 8, 48, 32, 64
+    g = torch.Generator(device=DEV).manual_seed(19)
+    x = torch.randn((B, S, S, S, cin), device=DEV, generator=g)
+    w = torch.randn((cout, cin, 3, 3, 3), device=DEV, generator=g) * (27 * cin) ** -0.5
+    sc = 1 + 0.2 * torch.randn((cout,), device=DEV, generator=g)
+    sh = 0.2 * torch.randn((cout,), device=DEV, generator=g)
+    uf, _ = ops.pack_weights_wino(w, True, False)
+    y = _wino_eval_block(x, uf, sc, sh, cin, cout, "max")
+    z, _, _ = ops.conv3d_wino_raw(x, uf, cin, cout, False)
+    y2 = torch.empty_like(y)
+    _lib.call("tmf_bn_act_pool_fwd_t", z.data_ptr(), sc.data_ptr(), sh.data_ptr(), y2.data_ptr(), B, S, S, S, cout,
+              _lib.pool_code("max"), 0.01, 0, ops._stream())
+    assert torch.equal(y, y2)
 
 
 @pytest.mark.parametrize("scale", [1.0, 1000.0])

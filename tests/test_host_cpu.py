@@ -294,6 +294,23 @@ def test_winograd_form_is_the_default_plan_of_the_encoder():
         lib.tmf_set_option(b"conv_wino", 3)
 
 
+def test_winograd_workgroup_cap_sizes_the_statistic_rows():
+    """tmf_set_option("wino_cus", n): the persistent Winograd kernels' workgroup count — and with it the statistic rows the
+    caller allocates — is capped at min(n, compute units); 0 returns to the device's count (256 without a device)."""
+    from transmf_ad_amd import _lib
+    lib = _lib.load()
+    rows = lib.tmf_conv3d_wino_stat_blocks(8, 48, 48, 48)
+    try:
+        assert lib.tmf_set_option(b"wino_cus", 5) == 0
+        assert lib.tmf_conv3d_wino_stat_blocks(8, 48, 48, 48) == 5 and lib.tmf_conv3d_wino_stat_blocks(2, 7, 9, 13) == 5
+        assert lib.tmf_set_option(b"wino_cus", 1 << 20) == 0
+        assert lib.tmf_conv3d_wino_stat_blocks(8, 48, 48, 48) == rows                 # (never above the device's count)
+        assert lib.tmf_set_option(b"wino_cus", -1) != 0
+    finally:
+        assert lib.tmf_set_option(b"wino_cus", 0) == 0
+    assert lib.tmf_conv3d_wino_stat_blocks(8, 48, 48, 48) == rows
+
+
 def test_algorithm_choice_travels_in_the_descriptor():
     """tmf_snet_desc.flags with TMF_SNET_ALGO: the plan of a call (here: the size of its `saved` workspace, host arithmetic)
     follows the descriptor, not the process options — and without the bit it follows the options; tmf_snet_algo_flags() is the

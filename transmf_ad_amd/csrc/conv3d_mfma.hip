@@ -1666,6 +1666,10 @@ extern "C" int tmf_set_option(const char* name, int value) {
     }
     if (strcmp(name, "wino_p") == 0) return tmf_wino_p_set(value);
     if (strcmp(name, "wino_x") == 0) return tmf_wino_x_set(value);
+    if (strcmp(name, "wino_cus") == 0) {
+        TMF_REQUIRE(value >= 0, TMF_E_ARG, "tmf_set_option: wino_cus must be >= 0, got %d", value);
+        return tmf_wino_cus_set(value);
+    }
     if (strcmp(name, "c1_gram") == 0) return tmf_c1_gram_set(value);
     if (strcmp(name, "c1_split") == 0) return tmf_c1_split_set(value);
     if (strcmp(name, "conv_wino") == 0) {

@@ -35,6 +35,7 @@
 // same tolerances as the direct path.
 //
 // Replaces aten::conv3d / convolution_backward at /root/reference/models/networks.py:28,31,37,40,46.
+#include <atomic>
 #include <type_traits>
 #include "tmf_common.h"
 
@@ -1804,6 +1805,10 @@ int wino_p_mode() {
     return g_wino_p;
 }
 
+// tmf_set_option("wino_cus", n): n > 0 caps the persistent workgroups (and statistic rows) at min(n, compute units), 0 = the device's
+// count or TMF_WINO_CUS.  Process-wide, read before the per-thread cache of the device's count.
+std::atomic<int> g_wino_cus{0};
+
 int wino_cu_count() {
     static thread_local int n[16] = {};
     int dev = 0;
@@ -1812,11 +1817,14 @@ int wino_cu_count() {
     if (n[dev] == 0) {
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        const char* e = getenv("TMF_WINO_CUS");             // experiments: fewer persistent workgroups than compute units
-        if (e && atoi(e) > 0 && atoi(e) < v) v = atoi(e);
         n[dev] = v;
     }
-    return n[dev];
+    int cap = g_wino_cus.load(std::memory_order_relaxed);
+    if (cap <= 0) {
+        static const int env = getenv("TMF_WINO_CUS") ? atoi(getenv("TMF_WINO_CUS")) : 0;   // experiments: fewer persistent workgroups than compute units
+        cap = env;
+    }
+    return cap > 0 && cap < n[dev] ? cap : n[dev];
 }
 
 // Brick geometry of the persistent kernel for a volume: 1 (four samples x 4x4x4) where that executes fewer tiles than 0 (4x8x8)
@@ -1892,6 +1900,7 @@ int launch_wino_p(const char* what, const float* x, const float* u, float* z, fl
 }  // namespace
 
 int tmf_wino_p_set(int v) { g_wino_p = v ? 1 : 0; return TMF_OK; }
+int tmf_wino_cus_set(int v) { g_wino_cus.store(v, std::memory_order_relaxed); return TMF_OK; }
 extern "C" int tmf_wino_p_mode(void) { return wino_p_mode(); }
 
 #ifdef TMF_WINO_TRACE

@@ -91,6 +91,7 @@ int tmf_conv3d_stat_blocks_mode(int B, int D, int H, int W, int cin, int cout, i
 int tmf_c1_split_set(int v);     // conv1_fused.hip: tmf_set_option("c1_split", 0 | 1): z of the first block (fp32) as exact 3-way bf16 splits
 int tmf_c1_gram_set(int v);      // conv1_gram.hip: tmf_set_option("c1_gram", 0 | 1): the first block through the tap Gram matrix of its input
 int tmf_wino_p_set(int v);       // conv3d_wino.hip: tmf_set_option("wino_p", 0 | 1): two-waves-per-SIMD / persistent one-wave-per-SIMD forward kernel
+int tmf_wino_cus_set(int v);     // conv3d_wino.hip: tmf_set_option("wino_cus", n): persistent Winograd workgroups capped at min(n, compute units), 0 = device / TMF_WINO_CUS
 // per-call algorithm choice (tmf_snet_desc.flags & TMF_SNET_ALGO): the whole-encoder entries set it for the calling thread while they
 // plan and enqueue; the option getters (tmf_conv_wino_mode, wino_p_mode, wino_x_mode, c1_gram_mode) look here first
 int  tmf_algo_override(void);            // 0, or a flags word with TMF_SNET_ALGO set
