@@ -342,14 +342,14 @@ int tmf_layernorm_bwd(const float* x, const float* gamma, const float* mean, con
  * residual (:131-141, 227), and the matching backward passes.
  *
  * forward:  y = [GELU]( LayerNorm?(x) . w^T + bias ) + residual
- *   x [R][K], w [Nout][K] (nn.Linear layout), y [R][Nout]; K % 16 == 0, Nout % 128 == 0.
- *   ln_gamma != NULL: LayerNorm over K first (K must be 128); writes ln_mean / ln_rstd [R] and, when
+ *   x [R][K], w [Nout][K] (nn.Linear layout), y [R][Nout]; K % 16 == 0, Nout % 64 == 0.
+ *   ln_gamma != NULL: LayerNorm over K first (K must be 64, 128 or 256); writes ln_mean / ln_rstd [R] and, when
  *   ln_out != NULL, the normalised rows [R][K].  bias [Nout] and residual [R][Nout] may be NULL.
  *   gelu_pre != NULL: gelu_pre = (..) . w^T + bias and y = GELU(gelu_pre) (erf form); no residual then.
- * backward (input gradient):  dx = E( dy . w ),  dy [R][Nout], w [Nout][K], dx [R][K]; Nout % 16 == 0, K % 128 == 0.
+ * backward (input gradient):  dx = E( dy . w ),  dy [R][Nout], w [Nout][K], dx [R][K]; Nout % 16 == 0, K % 64 == 0.
  *   gelu_pre != NULL: E(v) = v * GELU'(gelu_pre), gelu_pre [R][K].
- *   ln_x != NULL (K == 128): E(v) = LayerNormBackward(v; ln_x, ln_mean, ln_rstd, ln_gamma) + add1 + add2, and the
- *   row-block partials of dgamma / dbeta go to ln_partial[blk * partial_stride + {0..127 | 128..255}].
+ *   ln_x != NULL (K of 64, 128 or 256): E(v) = LayerNormBackward(v; ln_x, ln_mean, ln_rstd, ln_gamma) + add1 + add2,
+ *   and the row-block partials of dgamma / dbeta go to ln_partial[blk * partial_stride + {0..K-1 | K..2K-1}].
  *   otherwise E(v) = v + add1.   add1 / add2 [R][K] may be NULL.
  *   bias_partial != NULL: column sums of the block's dy rows -> bias_partial[blk * partial_stride + c], c < Nout.
  *   blk < tmf_tok_row_blocks(R); reduce the partials with tmf_colsum_finalize(partial, nblk, partial_stride, ..).
@@ -525,7 +525,8 @@ int    tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const tmf_sne
  * forward, or of its backward.  Replaces `self.fuse_transformer(mri_embeddings, pet_embeddings)` (models/mymodel.py:220
  * -> networks.py:272-281: depth x [mri <- Transformer(mri | pet) + mri; pet <- Transformer(pet | NEW mri) + pet], then
  * cat[mean, mean, max, max] over tokens) and its slice of `all_loss.backward()`.  Dropout (options/option.py:39) enters as
- * keep-masks in tmf_xformer_params.  dim == 128; heads*dim_head and mlp multiples of 128.
+ * keep-masks in tmf_xformer_params.  dim of 64, 128 or 256; heads*dim_head and mlp multiples of 64.  Dims other than
+ * 128 always run one launch per op, and take no keep-masks.
  *
  * inst[2*l] / inst[2*l + 1] = the mri / pet Transformer(depth=1) of layer l, parameters = the reference's state_dict
  * tensors (nn.Linear weights (out, in)).  Gradients: small = [b2 (dim) | b1 (mlp) | bo (dim) | ln2 gamma | ln2 beta |

@@ -46,9 +46,12 @@ int check_desc(const char* fn, const tmf_fusion_desc* d) {
     TMF_REQUIRE_PTR(d);
     TMF_REQUIRE(d->B > 0 && d->N > 0 && d->depth >= 0 && d->depth <= TMF_FUSION_MAX_DEPTH, TMF_E_SHAPE,
                 "%s: B=%d N=%d depth=%d (depth <= %d)", fn, d->B, d->N, d->depth, TMF_FUSION_MAX_DEPTH);
-    TMF_REQUIRE(d->dim == 128 && d->heads > 0 && d->dim_head > 0 && (d->heads * d->dim_head) % 128 == 0 && d->mlp % 128 == 0,
-                TMF_E_SHAPE, "%s: needs dim == 128 and heads*dim_head, mlp multiples of 128 (dim=%d inner=%d mlp=%d)", fn,
-                d->dim, d->heads * d->dim_head, d->mlp);
+    // dim: the widths token_gemm.hip's LayerNorm prologue / LayerNorm-backward epilogue take (dims other than 128 always
+    // run one launch per op: tmf_xf_supported answers no for them)
+    TMF_REQUIRE((d->dim == 64 || d->dim == 128 || d->dim == 256) && d->heads > 0 && d->dim_head > 0 &&
+                (d->heads * d->dim_head) % 64 == 0 && d->mlp % 64 == 0,
+                TMF_E_SHAPE, "%s: needs dim of 64, 128 or 256 and heads*dim_head, mlp multiples of 64 (dim=%d inner=%d mlp=%d)",
+                fn, d->dim, d->heads * d->dim_head, d->mlp);
     TMF_REQUIRE(d->dim_head == 8 || d->dim_head == 16 || d->dim_head == 32 || d->dim_head == 64, TMF_E_SHAPE,
                 "%s: dim_head=%d must be 8, 16, 32 or 64", fn, d->dim_head);
     return TMF_OK;

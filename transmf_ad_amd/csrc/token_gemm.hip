@@ -6,20 +6,25 @@
 // 219-230, 262-263) — 13 kernels forward and ~40 backward when each op is its own launch, all of them 3-15 us
 // and serial.  Here every Linear is ONE launch that also does its neighbours' element-wise work:
 //
-//   forward   y  = [GELU]( LayerNorm?(x) . W^T + bias ) + residual        tok_gemm_kernel<false, LN, EPI>
-//   backward  dx = LayerNormBackward?( (dy . W) [* GELU'(h)] ) + add1 + add2   tok_gemm_kernel<true, false, EPI>
+//   forward   y  = [GELU]( LayerNorm?(x) . W^T + bias ) + residual        tok_gemm_kernel<false, LNK, EPI, CT>
+//   backward  dx = LayerNormBackward?( (dy . W) [* GELU'(h)] ) + add1 + add2   tok_gemm_kernel<true, 0, EPI, CT>
 //             + the bias-gradient column sums of dy and the LayerNorm dgamma / dbeta block partials
 //
-// Tile: 16 token rows x 128 output columns per workgroup of 4 wavefronts (2 MFMA column tiles each),
-// v_mfma_f32_16x16x4_f32 (exact fp32).  The A tile (after the LayerNorm prologue) sits in LDS and is read
-// with one ds_read_b128 per 4 MFMAs through a K-permutation (lane group kb takes k = 16 s + 4 kb + j); the
+// Tile: 16 token rows x TN = 64 CT output columns per workgroup of 4 wavefronts (CT = 1, 2 or 4 MFMA column tiles
+// each), v_mfma_f32_16x16x4_f32 (exact fp32).  The A tile (after the LayerNorm prologue) sits in LDS and is read
+// with one ds_read_b128 per 4 CT MFMAs through a K-permutation (lane group kb takes k = 16 s + 4 kb + j); the
 // weights come straight from L2 in the matching order (one 16-B load per 4 MFMAs in the W^T form).
+// Tile choice (the host entries below): 128 columns (CT = 2) for every shape a multiple of 128 wide — the model's
+// dim-128 layers; 64 columns where the output width is only a multiple of 64 (dim 64).  The LayerNorm-backward epilogue
+// needs a whole row per workgroup, so there the tile IS the row: 64, 128 or 256 columns for dim 64, 128, 256.
 // Weight gradients stay plain GEMMs (dy^T . saved activations).
+#include <type_traits>
 #include "tmf_common.h"
 
 namespace {
 
-constexpr int TM = 16, TN = 128, TTHR = 256;
+constexpr int TM = 16, TTHR = 256;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct TokArgs {
     const float* A; const float* W; float* Y;
@@ -44,10 +49,26 @@ __device__ __forceinline__ float half_sum(float v) {         // sum over the 32 
     return v;
 }
 
+// LayerNorm prologue on one lane's chunk of a row (f32x4 or f32x2)
+__device__ __forceinline__ float hsum(f32x4 v) { return v[0] + v[1] + v[2] + v[3]; }
+__device__ __forceinline__ float hsum(f32x2 v) { return v[0] + v[1]; }
+__device__ __forceinline__ f32x4 minus(f32x4 v, float mu) { return f32x4{v[0] - mu, v[1] - mu, v[2] - mu, v[3] - mu}; }
+__device__ __forceinline__ f32x2 minus(f32x2 v, float mu) { return f32x2{v[0] - mu, v[1] - mu}; }
+__device__ __forceinline__ float sumsq(f32x4 d) { return d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]; }
+__device__ __forceinline__ float sumsq(f32x2 d) { return d[0] * d[0] + d[1] * d[1]; }
+__device__ __forceinline__ f32x4 affine(f32x4 d, float rs, f32x4 g, f32x4 b) {
+    return f32x4{d[0] * rs * g[0] + b[0], d[1] * rs * g[1] + b[1], d[2] * rs * g[2] + b[2], d[3] * rs * g[3] + b[3]};
+}
+__device__ __forceinline__ f32x2 affine(f32x2 d, float rs, f32x2 g, f32x2 b) {
+    return f32x2{d[0] * rs * g[0] + b[0], d[1] * rs * g[1] + b[1]};
+}
+
 enum { EPI_PLAIN = 0, EPI_GELU = 1, EPI_GELU_GRAD = 2, EPI_LN_BWD = 3 };
 
-template <bool NN, bool LN, int EPI>
+// LNK: row width of the LayerNorm prologue (64, 128 or 256), 0 = none.  CT: MFMA column tiles per wave.
+template <bool NN, int LNK, int EPI, int CT>
 __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   // <= 256 registers: MFMA results stay in VGPRs
+    constexpr int TN = 64 * CT;                    // output columns per workgroup
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int KP = p.K + 4;
     float* As = smem;                              // [16][K + 4]
@@ -56,10 +77,10 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, kb = lane >> 4;
     const int r0 = blockIdx.x * TM;
-    const int c0 = blockIdx.y * TN + wave * 32;
+    const int c0 = blockIdx.y * TN + wave * (16 * CT);
 
     // ---- A tile -> LDS ----
-    if (LN) {                                      // K == 128: a half-wave owns one row
+    if constexpr (LNK == 128) {                    // K == 128: a half-wave owns one row
         const int li = lane & 31;
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
@@ -78,6 +99,52 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
             *reinterpret_cast<f32x4*>(As + row * KP + li * 4) = a;
             if (blockIdx.y == 0 && gr < p.R) {
                 if (p.ln_out) *reinterpret_cast<f32x4*>(p.ln_out + (size_t)gr * p.K + li * 4) = a;
+                if (li == 0) { p.ln_mean[gr] = mu; p.ln_rstd[gr] = rs; }
+            }
+        }
+    } else if constexpr (LNK != 0) {               // K == 64 or 256: the same with K / 32 values per lane, held as NC
+        // chunks of VW contiguous floats, chunk c at column 32 VW c + VW li (each chunk one coalesced row segment).  The
+        // K == 128 branch above is this with NC = 1, VW = 4, kept as written so that its code stays unchanged.
+        constexpr int VW = LNK >= 128 ? 4 : 2, NC = LNK / (32 * VW);
+        typedef typename std::conditional<VW == 4, f32x4, f32x2>::type vec;
+        const int li = lane & 31;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int row = wave * 4 + pass * 2 + (lane >> 5);
+            const int gr = r0 + row;
+            vec v[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                v[c] = vec{};
+                if (gr < p.R) v[c] = *reinterpret_cast<const vec*>(p.A + (size_t)gr * p.K + 32 * VW * c + li * VW);
+            }
+            float s = hsum(v[0]);
+#pragma unroll
+            for (int c = 1; c < NC; ++c) s += hsum(v[c]);
+            const float mu = half_sum(s) * (1.f / LNK);
+            vec d[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) d[c] = minus(v[c], mu);
+            float q = sumsq(d[0]);
+#pragma unroll
+            for (int c = 1; c < NC; ++c) q += sumsq(d[c]);
+            const float var = half_sum(q) * (1.f / LNK);
+            const float rs = 1.f / sqrtf(var + p.eps);
+            vec a[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const vec g = *reinterpret_cast<const vec*>(p.ln_g + 32 * VW * c + li * VW);
+                const vec b = *reinterpret_cast<const vec*>(p.ln_b + 32 * VW * c + li * VW);
+                a[c] = affine(d[c], rs, g, b);
+                if (gr >= p.R) a[c] = vec{};
+                *reinterpret_cast<vec*>(As + row * KP + 32 * VW * c + li * VW) = a[c];
+            }
+            if (blockIdx.y == 0 && gr < p.R) {
+                if (p.ln_out) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c)
+                        *reinterpret_cast<vec*>(p.ln_out + (size_t)gr * p.K + 32 * VW * c + li * VW) = a[c];
+                }
                 if (li == 0) { p.ln_mean[gr] = mu; p.ln_rstd[gr] = rs; }
             }
         }
@@ -102,22 +169,25 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
         }
     }
 
-    // ---- MFMA: acc[t] = A[16 x K] . B[K x 16] for this wave's two column tiles ----
-    f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    // ---- MFMA: acc[t] = A[16 x K] . B[K x 16] for this wave's CT column tiles ----
+    f32x4 acc[CT] = {};
     const float* arow = As + m * KP + 4 * kb;
     const int nsteps = p.K >> 4;
     if (!NN) {
-        const float* w0 = p.W + (size_t)(c0 + m) * p.K + 4 * kb;
-        const float* w1 = w0 + (size_t)16 * p.K;
+        const float* wt[CT];
+        wt[0] = p.W + (size_t)(c0 + m) * p.K + 4 * kb;
+#pragma unroll
+        for (int t = 1; t < CT; ++t) wt[t] = wt[0] + (size_t)(16 * t) * p.K;
 #pragma unroll 4
         for (int s = 0; s < nsteps; ++s) {
             const f32x4 a4 = *reinterpret_cast<const f32x4*>(arow + 16 * s);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(w0 + 16 * s);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(w1 + 16 * s);
+            f32x4 b[CT];
+#pragma unroll
+            for (int t = 0; t < CT; ++t) b[t] = *reinterpret_cast<const f32x4*>(wt[t] + 16 * s);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b0[j], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b1[j], acc[1], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b[t][j], acc[t], 0, 0, 0);
             }
         }
     } else {
@@ -125,16 +195,16 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
 #pragma unroll 4
         for (int s = 0; s < nsteps; ++s) {
             const f32x4 a4 = *reinterpret_cast<const f32x4*>(arow + 16 * s);
-            float b0[4], b1[4];
+            float b[CT][4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                b0[j] = w0[(size_t)(16 * s + j) * p.N];
-                b1[j] = w0[(size_t)(16 * s + j) * p.N + 16];
+#pragma unroll
+                for (int t = 0; t < CT; ++t) b[t][j] = w0[(size_t)(16 * s + j) * p.N + 16 * t];
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b0[j], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b1[j], acc[1], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], b[t][j], acc[t], 0, 0, 0);
             }
         }
     }
@@ -142,7 +212,7 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
     // ---- epilogue.  D fragment: column = lane & 15, row = 4 * (lane >> 4) + r ----
     if (EPI == EPI_PLAIN || EPI == EPI_GELU || EPI == EPI_GELU_GRAD) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < CT; ++t) {
             const int col = c0 + t * 16 + m;
             const float bv = (EPI != EPI_GELU_GRAD && p.bias != nullptr) ? p.bias[col] : 0.f;
 #pragma unroll
@@ -163,8 +233,8 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
                 }
             }
         }
-    } else {                                        // LayerNorm backward over the 128 output columns (gridDim.y == 1)
-        float g[2][4], xh[2][4], s1[4], s2[4], pg[2] = {0.f, 0.f}, pb[2] = {0.f, 0.f};
+    } else {                                        // LayerNorm backward over the TN output columns (gridDim.y == 1)
+        float g[CT][4], xh[CT][4], s1[4], s2[4], pg[CT] = {}, pb[CT] = {};
         float rsr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -174,9 +244,9 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
             rsr[r] = ok ? p.lnb_rstd[gr] : 0.f;
             s1[r] = 0.f; s2[r] = 0.f;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
+            for (int t = 0; t < CT; ++t) {
                 const int col = c0 + t * 16 + m;
-                const float xv = ok ? p.lnb_x[(size_t)gr * 128 + col] : 0.f;
+                const float xv = ok ? p.lnb_x[(size_t)gr * TN + col] : 0.f;
                 xh[t][r] = (xv - mu) * rsr[r];
                 g[t][r] = acc[t][r] * p.lnb_g[col];
                 s1[r] += g[t][r];
@@ -194,13 +264,13 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
             if (m == 0) { red[(wave * 16 + 4 * kb + r) * 2] = s1[r]; red[(wave * 16 + 4 * kb + r) * 2 + 1] = s2[r]; }
         }
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < CT; ++t) {
             pg[t] += __shfl_xor(pg[t], 16); pg[t] += __shfl_xor(pg[t], 32);
             pb[t] += __shfl_xor(pb[t], 16); pb[t] += __shfl_xor(pb[t], 32);
-            if (kb == 0 && p.lnb_partial != nullptr) {
+            if (kb == 0 && p.lnb_partial != nullptr) {      // dgamma partials at columns 0..TN-1, dbeta at TN..2TN-1
                 const int col = c0 + t * 16 + m;
                 p.lnb_partial[(size_t)blockIdx.x * p.partial_stride + col] = pg[t];
-                p.lnb_partial[(size_t)blockIdx.x * p.partial_stride + 128 + col] = pb[t];
+                p.lnb_partial[(size_t)blockIdx.x * p.partial_stride + TN + col] = pb[t];
             }
         }
         __syncthreads();
@@ -210,11 +280,11 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
             float S1 = 0.f, S2 = 0.f;
 #pragma unroll
             for (int w = 0; w < 4; ++w) { S1 += red[(w * 16 + row) * 2]; S2 += red[(w * 16 + row) * 2 + 1]; }
-            S1 *= (1.f / 128.f); S2 *= (1.f / 128.f);
+            S1 *= (1.f / TN); S2 *= (1.f / TN);
             if (gr < p.R) {
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const size_t o = (size_t)gr * 128 + c0 + t * 16 + m;
+                for (int t = 0; t < CT; ++t) {
+                    const size_t o = (size_t)gr * TN + c0 + t * 16 + m;
                     float v = rsr[r] * (g[t][r] - S1 - xh[t][r] * S2);
                     if (p.add1 != nullptr) v += p.add1[o];
                     if (p.add2 != nullptr) v += p.add2[o];
@@ -225,11 +295,29 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
     }
 }
 
-template <bool NN, bool LN, int EPI>
+template <bool NN, int LNK, int EPI, int CT>
 int launch_tok(const TokArgs& a, hipStream_t s, const char* what) {
     const size_t lds = (size_t)(TM * (a.K + 4) + 4 * 16 * 2) * 4;
-    hipLaunchKernelGGL((tok_gemm_kernel<NN, LN, EPI>), dim3(tmf_cdiv(a.R, TM), a.N / TN), dim3(TTHR), lds, s, a);
+    hipLaunchKernelGGL((tok_gemm_kernel<NN, LNK, EPI, CT>), dim3(tmf_cdiv(a.R, TM), a.N / (64 * CT)), dim3(TTHR), lds, s, a);
     return tmf_launch_result(what);
+}
+
+// forward: 128-column tiles wherever Nout allows them (every shape accepted before 64-wide outputs were), else 64
+template <int LNK, int EPI>
+int launch_fwd(const TokArgs& a, hipStream_t s, const char* what) {
+    return a.N % 128 == 0 ? launch_tok<false, LNK, EPI, 2>(a, s, what) : launch_tok<false, LNK, EPI, 1>(a, s, what);
+}
+
+template <int LNK>
+int launch_fwd_ln(const TokArgs& a, bool gelu, hipStream_t s) {
+    if (gelu) return launch_fwd<LNK, EPI_GELU>(a, s, "tmf_tok_linear_fwd(ln,gelu)");
+    return launch_fwd<LNK, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd(ln)");
+}
+
+// backward input gradient, element-wise epilogues: the forward's rule over the output width K
+template <int EPI>
+int launch_bwd(const TokArgs& a, hipStream_t s, const char* what) {
+    return a.N % 128 == 0 ? launch_tok<true, 0, EPI, 2>(a, s, what) : launch_tok<true, 0, EPI, 1>(a, s, what);
 }
 
 }  // namespace
@@ -241,27 +329,25 @@ extern "C" int tmf_tok_linear_fwd(const float* x, const float* w, const float* b
                                   float* ln_mean, float* ln_rstd, float* ln_out, float* gelu_pre, void* stream) {
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(y);
     TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_fwd: non-positive dimension");
-    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % TN == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_fwd: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 128", K, Nout);
+    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % 64 == 0, TMF_E_SHAPE,
+                "tmf_tok_linear_fwd: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 64", K, Nout);
     TokArgs a = {};
     a.A = x; a.W = w; a.Y = y; a.R = R; a.K = K; a.N = Nout;
     a.bias = bias; a.res = residual; a.pre = gelu_pre;
     hipStream_t s = (hipStream_t)stream;
+    if (gelu_pre != nullptr)
+        TMF_REQUIRE(residual == nullptr, TMF_E_SHAPE, "tmf_tok_linear_fwd: GELU epilogue takes no residual");
     if (ln_gamma != nullptr) {
-        TMF_REQUIRE(K == 128, TMF_E_SHAPE, "tmf_tok_linear_fwd: the LayerNorm prologue needs K == 128 (got %d)", K);
+        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
+                    "tmf_tok_linear_fwd: the LayerNorm prologue needs K of 64, 128 or 256 (got %d)", K);
         TMF_REQUIRE_PTR(ln_beta); TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd);
         a.ln_g = ln_gamma; a.ln_b = ln_beta; a.eps = eps; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_out = ln_out;
-        if (gelu_pre != nullptr) {
-            TMF_REQUIRE(residual == nullptr, TMF_E_SHAPE, "tmf_tok_linear_fwd: GELU epilogue takes no residual");
-            return launch_tok<false, true, EPI_GELU>(a, s, "tmf_tok_linear_fwd(ln,gelu)");
-        }
-        return launch_tok<false, true, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd(ln)");
+        if (K == 64) return launch_fwd_ln<64>(a, gelu_pre != nullptr, s);
+        if (K == 128) return launch_fwd_ln<128>(a, gelu_pre != nullptr, s);
+        return launch_fwd_ln<256>(a, gelu_pre != nullptr, s);
     }
-    if (gelu_pre != nullptr) {
-        TMF_REQUIRE(residual == nullptr, TMF_E_SHAPE, "tmf_tok_linear_fwd: GELU epilogue takes no residual");
-        return launch_tok<false, false, EPI_GELU>(a, s, "tmf_tok_linear_fwd(gelu)");
-    }
-    return launch_tok<false, false, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd");
+    if (gelu_pre != nullptr) return launch_fwd<0, EPI_GELU>(a, s, "tmf_tok_linear_fwd(gelu)");
+    return launch_fwd<0, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd");
 }
 
 extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* dx, int R, int Nout, int K,
@@ -271,8 +357,8 @@ extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* 
                                         int partial_stride, void* stream) {
     TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(dx);
     TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_bwd_input: non-positive dimension");
-    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % TN == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 128", Nout, K);
+    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % 64 == 0, TMF_E_SHAPE,
+                "tmf_tok_linear_bwd_input: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 64", Nout, K);
     TMF_REQUIRE((ln_partial == nullptr && bias_partial == nullptr) || partial_stride > 0, TMF_E_SHAPE,
                 "tmf_tok_linear_bwd_input: partial_stride must be positive");
     TokArgs a = {};
@@ -281,16 +367,19 @@ extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* 
     a.lnb_partial = ln_partial; a.colsum_partial = bias_partial; a.partial_stride = partial_stride;
     hipStream_t s = (hipStream_t)stream;
     if (ln_x != nullptr) {
-        TMF_REQUIRE(K == 128 && gelu_pre == nullptr, TMF_E_SHAPE,
-                    "tmf_tok_linear_bwd_input: the LayerNorm-backward epilogue needs K == 128 and no GELU (K=%d)", K);
+        TMF_REQUIRE((K == 64 || K == 128 || K == 256) && gelu_pre == nullptr, TMF_E_SHAPE,
+                    "tmf_tok_linear_bwd_input: the LayerNorm-backward epilogue needs K of 64, 128 or 256 and no GELU (K=%d)", K);
         TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd); TMF_REQUIRE_PTR(ln_gamma);
         a.lnb_x = ln_x; a.lnb_mean = ln_mean; a.lnb_rstd = ln_rstd; a.lnb_g = ln_gamma;
-        return launch_tok<true, false, EPI_LN_BWD>(a, s, "tmf_tok_linear_bwd_input(ln)");
+        // one workgroup per row block holds whole rows: the tile is K wide
+        if (K == 64) return launch_tok<true, 0, EPI_LN_BWD, 1>(a, s, "tmf_tok_linear_bwd_input(ln)");
+        if (K == 128) return launch_tok<true, 0, EPI_LN_BWD, 2>(a, s, "tmf_tok_linear_bwd_input(ln)");
+        return launch_tok<true, 0, EPI_LN_BWD, 4>(a, s, "tmf_tok_linear_bwd_input(ln)");
     }
-    if (gelu_pre != nullptr) return launch_tok<true, false, EPI_GELU_GRAD>(a, s, "tmf_tok_linear_bwd_input(gelu)");
+    if (gelu_pre != nullptr) return launch_bwd<EPI_GELU_GRAD>(a, s, "tmf_tok_linear_bwd_input(gelu)");
     a.res = add1;                                                    // plain epilogue: + add1 (one residual gradient)
     TMF_REQUIRE(add2 == nullptr, TMF_E_SHAPE, "tmf_tok_linear_bwd_input: add2 needs the LayerNorm epilogue");
-    return launch_tok<true, false, EPI_PLAIN>(a, s, "tmf_tok_linear_bwd_input");
+    return launch_bwd<EPI_PLAIN>(a, s, "tmf_tok_linear_bwd_input");
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -276,7 +276,7 @@ class CrossTransformer_MOD_AVG(nn.Module):
         self.gmp = _TokenReduce("max")
 
     def _one_call_ok(self, mri_tokens):
-        """dim-128 geometry, depth-1 Transformer instances, dropout inactive, nobody listening on the inner modules:
+        """dim 64, 128 or 256, depth-1 Transformer instances, dropout inactive, nobody listening on the inner modules:
         the whole fusion is one library call per pass (ops.FusionTrain)."""
         if not (mri_tokens.is_cuda and torch.is_grad_enabled()) or len(self.layers) == 0:
             return False

@@ -936,8 +936,12 @@ def tok_wgrad_multi(pairs):
     return outs
 
 
+# the block widths token_gemm.hip's LayerNorm prologue / LayerNorm-backward epilogue take
+TOKEN_GEMM_DIMS = (64, 128, 256)
+
+
 def fused_block_supported(dim, inner, mlp):
-    return FUSE_TOKEN_LINEARS and dim == 128 and inner % 128 == 0 and mlp % 128 == 0
+    return FUSE_TOKEN_LINEARS and dim in TOKEN_GEMM_DIMS and inner % 64 == 0 and mlp % 64 == 0
 
 
 class TransformerLayer(torch.autograd.Function):
@@ -1088,7 +1092,7 @@ def dropout_keep_masks(requests, device):
 
 
 def fusion_one_call_supported(dim, inner, mlp, dim_head, depth):
-    return (FUSION_ONE_CALL and FUSE_TOKEN_LINEARS and dim == 128 and inner % 128 == 0 and mlp % 128 == 0
+    return (FUSION_ONE_CALL and FUSE_TOKEN_LINEARS and dim in TOKEN_GEMM_DIMS and inner % 64 == 0 and mlp % 64 == 0
             and dim_head in (8, 16, 32, 64) and 0 < depth <= 16)
 
 
