@@ -11,6 +11,11 @@ batch already resident in HBM: zero_grad, forward of model_ad(dim=128, depth=3, 
 dim_head=32, mlp_dim=512), CE + adversarial CE, backward, (gradient all-reduce over RCCL when
 N > 1), Adam step.  Workload (BASELINE.json configs[1]): batch 8 per GPU of 1x96^3 MRI+PET pairs,
 fp32.  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds everything else the benchmark measures or checks, as every run did before: the numerics gate against the
+CPU oracle, the per-launch roofline loop, the CPU baseline and (default workload, one GPU) the other BASELINE
+configurations as `also` records.
 """
 import argparse
 import json
@@ -407,7 +412,11 @@ def build_parser():
     ap.add_argument("--size", type=int, default=96)
     ap.add_argument("--shape", type=int, nargs=3, default=None, metavar=("D", "H", "W"),
                     help="non-cubic volumes, e.g. 91 109 91 (the ADNI volumes of the reference, datasets/ADNI.py:96)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the numerics gate against the CPU oracle, the per-launch roofline loop, the CPU "
+                         "baseline and, for the default workload on one GPU, the other BASELINE configurations (`also`).  "
+                         "Without it a run times its steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no numerics gate")
     ap.add_argument("--cpu-batch", type=int, default=8, help="pairs in the bounded CPU sample (default 8; 2 above 96^3)")
     ap.add_argument("--cpu-threads", type=int, default=32)
     ap.add_argument("--precision", choices=["fp32", "bf16", "fp32x"], default="fp32",
@@ -431,7 +440,7 @@ def build_parser():
                          "(kfold_train_adversarial.py:127-128); the default step has them")
     ap.add_argument("--roofline-only", action="store_true",
                     help="skip the train-step timing: only the dominant-kernel loop (so that a rocprofv3 --stats run "
-                         "of this command averages exactly the launches the roofline entry quotes)")
+                         "of this command averages exactly the launches the roofline entry quotes); implies --full")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="model_ad(dropout=p): Dropout in the fusion block's Transformer instances (options/option.py:39; the "
                          "reference default and the headline are 0)")
@@ -440,8 +449,9 @@ def build_parser():
                          "gradients in the Winograd form F(2x2x2, 3x3x3) on the fp32 matrix pipe, 2 forward and data gradients, "
                          "1 data gradients only, 0 the direct kernels")
     ap.add_argument("--no-also", action="store_true",
-                    help="the default N=1 run measures the other BASELINE configurations in the same process after the headline "
-                         "(`also`: configs[2] 128^3 bf16, configs[4] both readings at batch 16, the fp32x mode); this skips them")
+                    help="a --full N=1 run of the default workload measures the other BASELINE configurations in the same "
+                         "process after the headline (`also`: configs[2] 128^3 bf16, configs[4] both readings at batch 16, the "
+                         "fp32x mode); this skips them")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the LAST timed step of the headline configuration handed its caller "
                          "as DIR/<name>.npy (rank 0): see dump_outputs.  The inputs and parameters are seeded, so the same "
@@ -478,8 +488,8 @@ def dump_outputs(out_dir, loss, outputs, net):
     return total
 
 
-# The other BASELINE.json configurations, measured in the SAME process after the headline when bench.py runs with its
-# default flags on one GPU (so that the driver's one run witnesses them): name -> argument overrides.
+# The other BASELINE.json configurations, measured in the SAME process after the headline when bench.py runs with --full
+# and otherwise default flags on one GPU (so that one run witnesses them): name -> argument overrides.
 ALSO = (
     ("configs[2]: 128^3, batch 8, bf16 MFMA 3D conv + bf16 activation storage",
      dict(precision="bf16", storage="bf16", size=128, batch=8, model="ad", cpu_batch=2, also_kernel_roofline=True)),
@@ -498,6 +508,26 @@ def _is_default_workload(args):
     return (args.model == "ad" and args.precision == "fp32" and args.storage == "fp32" and args.size == 96 and args.batch == 8
             and not args.shape and not args.eval and not args.from_host and not args.roofline_only and not args.no_item_sync
             and not args.no_cpu_baseline and args.steps > 0 and args.dropout == 0.0 and args.conv_wino == 3)
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.roofline_only:          # its one output is the roofline loop, which lives behind --full
+        args.full = True
+    return args
+
+
+def extra_legs(args, rank, world, brief=False):
+    """What a run measures beside its timed steps -> {gate, roofline, cpu, also}: the numerics gate against the CPU oracle,
+    the per-launch roofline loop, the CPU baseline, the `also` records.  All False without --full (a plain run); brief: an
+    `also` record itself."""
+    full = args.full and rank == 0
+    solo = full and world == 1 and not args.no_cpu_baseline
+    return {"gate": solo and not brief and args.model == "ad" and not args.shape and args.precision == "fp32",
+            "roofline": full and not args.eval and (not brief or getattr(args, "also_kernel_roofline", False)),
+            "cpu": solo,
+            "also": (full and world == 1 and not brief and not args.no_also and _is_default_workload(args)
+                     and os.environ.get("TMF_DDP_FORCE", "0") != "1")}
 
 
 def launch_command(argv, n_gpus, port, python=None):
@@ -534,7 +564,7 @@ def self_launch(args, argv):
 
 def main():
     import copy
-    args = build_parser().parse_args()
+    args = parse_args()
     if args.dump_outputs and (args.steps < 1 or args.roofline_only):
         raise SystemExit("--dump-outputs needs at least one timed step (--steps >= 1, no --roofline-only)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -554,8 +584,7 @@ def main():
 
     cpu_cache = {}
     out = run(args, rank, local, world, dev, cpu_cache, brief=False)
-    if rank == 0 and world == 1 and not args.no_also and _is_default_workload(args) \
-            and os.environ.get("TMF_DDP_FORCE", "0") != "1":
+    if extra_legs(args, rank, world)["also"]:
         also = []
         for title, over in ALSO:
             a = copy.copy(args)
@@ -583,8 +612,9 @@ def main():
 
 
 def run(args, rank, local, world, dev, cpu_cache, brief=False):
-    """One configuration: build the model, time the steps, measure the roofline / CPU baseline legs -> the record (rank 0;
-    None elsewhere).  brief: an `also` record — whole-step roofline only (no per-launch loop), no numerics gate."""
+    """One configuration: build the model, time the steps, measure the roofline / CPU baseline legs of extra_legs -> the
+    record (rank 0; None elsewhere).  brief: an `also` record — whole-step roofline only (no per-launch loop), no numerics
+    gate."""
     import statistics
     from transmf_ad_amd import model_ad, ops, _lib
     from transmf_ad_amd.parallel import GradAllReduce
@@ -619,11 +649,12 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
         from transmf_ad_amd.optim import Adam as OneLaunchAdam
         opt = OneLaunchAdam(net.parameters(), lr=1e-4)
     crit = nn.CrossEntropyLoss()
-    # BASELINE.md section 3 "same run also performs the numerics gate": the product's eval-mode forward at the bench's own
-    # initial parameters and inputs against the CPU oracle (<= 1e-3 on logits and loss); evaluated in the cpu_baseline leg
+    # BASELINE.md section 3 "same run also performs the numerics gate" (a --full run): the product's eval-mode forward at the
+    # bench's own initial parameters and inputs against the CPU oracle (<= 1e-3 on logits and loss); evaluated in the
+    # cpu_baseline leg
     gate_state = None
-    want_gate = (rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "ad" and not args.shape
-                 and args.precision == "fp32" and not brief)
+    legs = extra_legs(args, rank, world, brief)
+    want_gate = legs["gate"]
     if want_gate:
         gate_state = {k: v.detach().cpu().clone() for k, v in (net.module if hasattr(net, "module") else net).state_dict().items()}
     B, S = args.batch, args.size
@@ -830,7 +861,7 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
                                   c1_split=args.precision in ("fp32", "fp32x") and c1_split_on())
     ex_pair = {("bf16" if args.precision == "bf16" and k == "fp32" else k): v * half for k, v in ex_pair.items()}
     if rank == 0 and not args.eval:
-        if brief and not getattr(args, "also_kernel_roofline", False):
+        if not legs["roofline"]:         # a plain run or an `also` record: the whole step's figures, no launches of their own
             roof = {"whole_step": whole_step_entry(pairs_per_s, world, gf_pair, by_pair, args.precision, ex_pair)}
             if args.precision == "fp32x":
                 roof["peak_note"] = ("fractions price fp32 products against the fp32-MFMA peak (157.3 TF); the forward / "
@@ -851,7 +882,7 @@ def run(args, rank, local, world, dev, cpu_cache, brief=False):
     cpu_batch = args.cpu_batch
     if S > 96 and cpu_batch == 8:
         cpu_batch = 2                      # bounded sample (the contract's 10-30 s of CPU work): 128^3 steps are 2.4x as long
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if legs["cpu"]:
         from oracle import tmf_oracle as O         # test infrastructure, used ONLY as the timed CPU baseline
         omodel = {"ad": "model_ad", "cnn": "model_CNN_ad", "single": "model_single"}[args.model]
         key = (omodel, cpu_batch, vol)

@@ -511,3 +511,28 @@ def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--dump-outputs needs at least one timed step" in r.stderr
     assert not os.path.exists(tmp_path / "e")
+
+
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """`bench.py --steps K --warmup W` measures the headline alone; the numerics gate, the per-launch roofline loop, the CPU
+    baseline and the `also` records come with --full, where they keep their old conditions (bench.extra_legs)."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    none = dict(gate=False, roofline=False, cpu=False, also=False)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False
+    assert bench.extra_legs(plain, 0, 1) == none
+    for argv in (["--eval"], ["--precision", "bf16"], ["--no-cpu-baseline"], ["--dump-outputs", "d"]):
+        assert bench.extra_legs(bench.parse_args(argv), 0, 1) == none, argv
+    full = bench.parse_args(["--full", "--steps", "20", "--warmup", "5"])
+    assert bench.extra_legs(full, 0, 1) == dict(gate=True, roofline=True, cpu=True, also=True)
+    assert bench.extra_legs(full, 1, 2) == none                                      # rank 0 alone reports
+    assert bench.extra_legs(full, 0, 2) == dict(none, roofline=True)                  # no CPU legs beside N > 1 ranks
+    assert bench.extra_legs(full, 0, 1, brief=True) == dict(none, roofline=False, cpu=True)
+    assert bench.extra_legs(bench.parse_args(["--full", "--no-also"]), 0, 1)["also"] is False
+    assert bench.extra_legs(bench.parse_args(["--full", "--no-cpu-baseline"]), 0, 1) == dict(none, roofline=True)
+    assert bench.extra_legs(bench.parse_args(["--full", "--eval"]), 0, 1) == dict(none, gate=True, cpu=True)
+    # --roofline-only asks for nothing but the roofline loop: it implies --full
+    ro = bench.parse_args(["--roofline-only", "--no-cpu-baseline"])
+    assert ro.full is True and bench.extra_legs(ro, 0, 1) == dict(none, roofline=True)

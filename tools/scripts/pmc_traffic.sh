@@ -5,7 +5,7 @@ O=$R/gpurun_out/pmctraffic
 rm -rf $O; mkdir -p $O
 cd $R
 run() { n=$1; c=$2; shift 2
-  TMF_ROOF_REPS=3 TMF_ROOF_SPIN_S=0.3 timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/$n -o $n --output-format csv -- python3 bench.py --roofline-only --no-cpu-baseline "$@" > $O/$n.log 2>&1
+  TMF_ROOF_REPS=3 TMF_ROOF_SPIN_S=0.3 timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/$n -o $n --output-format csv -- python3 bench.py --full --roofline-only --no-cpu-baseline "$@" > $O/$n.log 2>&1
 }
 run f32_fetch FETCH_SIZE
 run f32_write WRITE_SIZE
