@@ -15,7 +15,9 @@
  *  - Activations are channels-last:  x[b][d][h][w][c]  ("NDHWC").
  *  - 3x3x3 weights are tap-major:    w[kd*9+kh*3+kw][cin][cout]; 1x1x1: w[cin][cout].
  *  - `stream` is a hipStream_t passed as void*; every call is asynchronous on it,
- *    never synchronises, never allocates, never throws.  Stateless and re-entrant.
+ *    never synchronises, never allocates, never throws.  Re-entrant: no state is
+ *    kept between calls, but the kernel choice follows the process options
+ *    (tmf_set_option below), which a call carrying TMF_SNET_ALGO overrides with its own.
  *  - Return: 0 = launched; <0 = TMF_E_* argument error (nothing launched);
  *    >0 = hipError_t from the launch.  tmf_last_error_string() describes the last
  *    non-zero return on the calling thread.
@@ -48,16 +50,41 @@ extern "C" {
 
 int         tmf_version(void);                 /* ABI version, currently 1 */
 const char* tmf_last_error_string(void);
-/* Process-wide tuning knobs (never change results).  "conv_waves" = 2 | 4 | 8 | 16: workgroup shape of the
- * convolution kernels (16, the default: two 8-wave workgroups per CU).  "conv_rt" = 0 | 1 | 2: the register-tiled fp32
- * forward / data-gradient kernel (6x6x12 bricks, csrc/conv3d_mfma.hip conv3d_fwd_rt_kernel) never (default) / for volumes of
- * at most 24^3 voxels that its bricks tile exactly, cin and cout multiples of 16 / wherever the bricks fit (results equal
- * up to fp32 summation order; tmf_conv3d_stat_blocks and tmf_conv3d_fwd_kernel_name follow the choice).  "bf16_v2" = 0 | 1 | 2:
- * bf16 forward / data-gradient kernel with 8x8x8 bricks and 2 x 2 register tiles never / by brick count (default) /
- * always (results equal up to fp32 summation order; tmf_conv3d_bf16_stat_blocks follows the choice).  "wgrad_tr" = 0 | 1 | 2:
- * bf16 weight-gradient kernel with LDS transposing reads never / where it is the faster one (default) / wherever its
- * shape rule allows (cin, cout multiples of 8); equal up to fp32 summation order.  "debug": timing ablations only, live in
- * -DTMF_ABLATE builds (results are garbage when set).
+/* Process options: tmf_set_option(name, value) or, where listed, an environment variable read once on first use; a value set
+ * wins over the environment.  0 on success; TMF_E_ARG for an unknown name or a value the option refuses (the table's "set").
+ * Process-wide, safe to call from any thread; a launch plans with the values of the moment.  Each option chooses kernels only:
+ * results stay equal up to fp32 summation order ("debug" aside).  Options marked "per call" are also carried by
+ * tmf_snet_desc.flags (TMF_SNET_ALGO, below): such a call follows its own word, not the process option.
+ *
+ *  option       set                      environment (atoi)            default  per call  chooses
+ *  conv_wino    0..3                     TMF_CONV_WINO: 0..2, else 3   3        yes       Winograd form for: 0 none, 1 data gradients,
+ *                                                                                         2 + forward, 3 + weight gradients (tmf_conv_wino_mode)
+ *  wino_p       any, non-zero -> 1       TMF_WINO_P: 0, else 1         1        yes       persistent Winograd kernels (tmf_wino_p_mode)
+ *  wino_x       any, non-zero -> 1       TMF_WINO_X: 0, else 1         1        yes       Winograd as exact bf16 splits (tmf_wino_x_mode)
+ *  c1_gram      <=0 -> 0, >=2 -> 2, 1    TMF_C1_GRAM: the same         1        yes       first block through its tap Gram matrix;
+ *                                                                                         2 in the bf16 mode as well (tmf_c1_gram_bytes)
+ *  c1_split     any, non-zero -> 1       TMF_C1_SPLIT: 0, else 1       1        yes       first block's z as exact bf16 splits (tmf_c1_split_mode)
+ *  wino_cus     >= 0; 0: the environment TMF_WINO_CUS                  0        no        n > 0 caps the persistent Winograd workgroups at
+ *                                                                                         min(n, compute units); 0 the device's count
+ *  conv_rt      0..2                     TMF_CONV_RT: 1, 2, else 0     0        no*       register-tiled fp32 forward / data-gradient
+ *                                                                                         kernel: never / volumes <= 24^3 / wherever it fits
+ *  conv_waves   2, 4, 8, 16              TMF_CONV_WAVES: 2, 4, 8,      16       no        workgroup shape of the direct convolutions
+ *                                        else 16
+ *  bf16_v2      0..2                     TMF_BF_V2: 0, 2, else 1       1        no        bf16 forward with 8x8x8 bricks: never / by brick
+ *                                                                                         count / always (tmf_conv3d_bf16_stat_blocks follows)
+ *  bf16_dma     0, 1                     -                             1        no        LDS-DMA form of that kernel (bf16 tensors)
+ *  wgrad_tr     0..2                     -                             1        no        bf16 weight gradient with transposing LDS reads:
+ *                                                                                         never / where faster / wherever cin, cout % 8 == 0
+ *  debug        any                      -                             0        no        timing-ablation bits of the direct kernels, in bf16
+ *                                                                                         only in -DTMF_ABLATE builds (results are garbage)
+ *  (none)       -                        TMF_WINO_EVEN, TMF_WINOX_SWAP, TMF_BF_NT2, TMF_CONV_AUTO: 0 turns off (default on) an
+ *                                        even persistent Winograd grid, the transposed split-kernel items, 64-channel bf16
+ *                                        workgroups, the per-launch brick choice of the direct forward
+ *  (none)       -                        TMF_C1_BLOCKS (default 1024; below 64 the default), TMF_C1_FWD_MULT (default 4):
+ *                                        workgroups of the first block's slab passes / multiple of them for its forward
+ *  * conv_rt: a call with TMF_SNET_ALONE asks for at least 1 for itself.
+ * The kernel-name and size queries (tmf_conv3d_fwd_kernel_name, tmf_conv3d_stat_blocks, tmf_conv3d_wino_stat_blocks, ...)
+ * follow the options of the moment: a buffer sized under one setting must not be launched under another.
  * Size limits of the convolution entries: one sample of a layer (D*H*W*max(cin, cout)) and one weight tensor stay below
  * 2^29 elements — offsets inside a sample are 32-bit byte offsets of buffer resources; violating shapes return TMF_E_SHAPE. */
 int         tmf_set_option(const char* name, int value);
@@ -131,9 +158,7 @@ int  tmf_conv3d_split_stat_blocks(int B, int D, int H, int W);        /* rows of
  * tmf_pack_conv_weights_wino (forward: u_fwd; data gradient: the same entry called with dz, u_dgrad and the channel
  * counts swapped); stat_partial (may be NULL): [tmf_conv3d_wino_stat_blocks()][2][cout].  Results differ from the direct
  * kernels' by fp32 rounding only (about twice their distance to the fp64 value).
- * tmf_conv_wino_mode(): tmf_set_option("conv_wino", 0 | 1 | 2 | 3) / TMF_CONV_WINO — 0 never (the direct kernels), 1 the data
- * gradients, 2 forward and data gradients, 3 (default) forward, data and weight gradients of the train-mode encoder blocks
- * that qualify. */
+ * tmf_conv_wino_mode(): the option "conv_wino" (tmf_set_option) — which train-mode encoder blocks that qualify take this form. */
 int    tmf_conv3d_fwd_wino(const float* x, const float* u, float* z, float* stat_partial,
                            int B, int D, int H, int W, int cin, int cout, void* stream);
 int    tmf_conv3d_wino_ok(int cin, int cout);
@@ -156,21 +181,20 @@ const char* tmf_conv3d_wino_kernel_name2(int B, int D, int H, int W, int cin, in
                                                                        * split kernel conv3d_winox_kernel where it takes the launch */
 size_t tmf_conv3d_wino_weight_bytes(int cin, int cout);             /* 64 * cin * cout floats + the same numbers as three bf16 parts
                                                                        * (6 bytes each) behind them */
-/* tmf_wino_x_mode(): tmf_set_option("wino_x", 0 | 1) / TMF_WINO_X — 1 (default): tmf_conv3d_fwd_wino (train forward and data gradient)
+/* tmf_wino_x_mode(): the option "wino_x" (tmf_set_option).  1: tmf_conv3d_fwd_wino (train forward and data gradient)
  * runs csrc/conv3d_winox.hip where cin % 32 == 0, cout % 32 == 0 and the volume takes 4x8x8 bricks: the SAME fp32 products, each
  * operand split exactly into three bf16 numbers (no rounding: 8 + 8 + 8 significand bits), six of the nine partial products on
  * v_mfma_f32_32x32x16_bf16 with fp32 accumulation — the dropped three are below 2^-24 of the product, under the rounding of the
  * fp32 product itself.  0: the fp32 matrix pipe (conv3d_wino_p_kernel) everywhere. */
 int    tmf_wino_x_mode(void);
 int    tmf_conv_wino_mode(void);
-/* tmf_wino_p_mode(): tmf_set_option("wino_p", 0 | 1) / TMF_WINO_P — 1 (default): the three Winograd entries run their persistent
+/* tmf_wino_p_mode(): the option "wino_p" (tmf_set_option).  1: the three Winograd entries run their persistent
  * one-wave-per-SIMD kernels (conv3d_wino_p_kernel, conv3d_wino_wgrad_p_kernel; the forward picks per volume between 4x8x8
  * bricks of one sample and 4x4x4 bricks of four samples — tmf_conv3d_wino_bricks() follows it); 0: the two-waves-per-
  * SIMD kernels of round 4.  Same results up to fp32 rounding of the output transform's order of additions. */
 int    tmf_wino_p_mode(void);
-/* tmf_set_option("wino_cus", n) — a test and experiment aid: n > 0 caps the workgroups of the persistent Winograd forward / data-
- * gradient kernels at min(n, compute units), so that every workgroup walks many items and launches split into windows of
- * n x (item table) items; 0 (default) returns to the device's count (or TMF_WINO_CUS).  Process-wide.  tmf_conv3d_wino_stat_blocks
+/* The option "wino_cus" (tmf_set_option) — a test and experiment aid: with n > 0 every workgroup of the persistent Winograd forward /
+ * data-gradient kernels walks many items and launches split into windows of n x (item table) items.  tmf_conv3d_wino_stat_blocks
  * follows it: a statistics buffer sized under one setting must not be launched under a larger one. */
 /* Weight gradient in the same form: dU_p = V_p^T Z_p per position of the transformed tile (V = the forward's input transform of
  * x, Z = A dz A^T), summed over all tiles on the fp32 matrix pipe, then dw = G^T dU G (fp64) — replaces the weight gradient of
@@ -199,8 +223,8 @@ int    tmf_conv3d_c1_wgrad(const float* x, const float* dz, float* dw, void* wor
  * ---------------------------------------------------------------------------- */
 int    tmf_c1_blocks(int B, int D, int H, int W, int C);
 int    tmf_c1_stats(const float* x, const float* w, float* stat_partial, int B, int D, int H, int W, int C, void* stream);
-/* Round 5: the first block through the tap Gram matrix of its INPUT (csrc/conv1_gram.hip; tmf_set_option("c1_gram", 0 | 1) /
- * TMF_C1_GRAM, default 1; fp32).  tmf_c1_stats_g: the statistics WITHOUT a convolution pass and the exact 27 x 27 matrix
+/* Round 5: the first block through the tap Gram matrix of its INPUT (csrc/conv1_gram.hip; the option "c1_gram" of tmf_set_option;
+ * fp32).  tmf_c1_stats_g: the statistics WITHOUT a convolution pass and the exact 27 x 27 matrix
  * G[t][t'] = sum_v x~(v + t) x~(v + t') of the zero-padded volume (+ the 27 shifted sums S_t), from 63 offset pair sums of the
  * volume minus per-face-class sums over the one-voxel shell around it, all in fp64 —
  * gram: tmf_c1_gram_bytes() bytes (0: not available — option "c1_gram" off or C > 64), doubles [0,729) G, [729,756) S_t, 756 S, then
@@ -476,7 +500,7 @@ int    tmf_scale_flip(const float* src, float* dst, const float* minmax, const u
 #define TMF_SNET_ALGO_C1_GRAM_BF16 0x4000         /* c1_gram 2: in the bf16 mode as well (off by default: slower there) */
 #define TMF_SNET_ALGO_C1_SPLIT 0x8000             /* c1_split: z of the first block (fp32) as exact 3-way bf16 splits on the bf16 pipe */
 int  tmf_snet_algo_flags(void);
-int  tmf_c1_split_mode(void);                     /* the process option "c1_split" (TMF_C1_SPLIT, default 1) or the calling entry's flags */
+int  tmf_c1_split_mode(void);                     /* the option "c1_split" (tmf_set_option) */
 typedef struct tmf_snet_desc {
     int   B, D, H, W;                /* input volumes (B, 1, D, H, W) */
     int   dim;                       /* sNet(dim) */

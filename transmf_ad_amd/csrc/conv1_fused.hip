@@ -594,12 +594,7 @@ Plan make_plan(int B, int D, int H, int W, int C, int target_blocks) {
 }
 // STATS / REDUCE / WGRAD write one slab per workgroup: keep them few (4 per CU: measured 0.772 ms for the four passes
 // against 0.796 at 8 per CU and 0.81 at 14-20; TMF_C1_BLOCKS overrides); FWD has no slab.
-static int slab_blocks() {
-    static int v = 0;
-    if (v == 0) { const char* e = getenv("TMF_C1_BLOCKS"); v = e ? atoi(e) : 1024; if (v < 64) v = 1024; }
-    return v;
-}
-#define SLAB_BLOCKS slab_blocks()
+#define SLAB_BLOCKS tmf_opt(TMF_OPT_C1_BLOCKS)
 
 int check(const char* fn, int B, int D, int H, int W, int C) {
     TMF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && C > 0, TMF_E_SHAPE, "%s: non-positive dimension", fn);
@@ -616,21 +611,10 @@ Args base_args(const float* x, const float* w, int D, int H, int W, int C, const
     return a;
 }
 
-int g_c1_split = -1;
-// tmf_set_option("c1_split", 0 | 1) / TMF_C1_SPLIT (default 1): the fp32 passes compute z as exact 3-way bf16 splits (SPLIT above)
-int c1_split_mode() {
-    if (const int o = tmf_algo_override()) return (o & TMF_SNET_ALGO_C1_SPLIT) ? 1 : 0;
-    if (g_c1_split < 0) {
-        const char* e = getenv("TMF_C1_SPLIT");
-        g_c1_split = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    return g_c1_split;
-}
+// "c1_split" 1 (default): the fp32 passes compute z as exact 3-way bf16 splits (SPLIT above)
+int c1_split_mode() { return tmf_opt(TMF_OPT_C1_SPLIT); }
 
 }  // namespace
-
-int tmf_c1_split_set(int v) { g_c1_split = v ? 1 : 0; return TMF_OK; }
-extern "C" int tmf_c1_split_mode(void) { return c1_split_mode(); }
 
 extern "C" int tmf_c1_blocks(int B, int D, int H, int W, int C) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
@@ -664,8 +648,7 @@ static int c1_bn_pool_fwd(bool bf16, bool p16, const float* x, const float* w, c
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift); TMF_REQUIRE_PTR(pooled);
     int rc = check("tmf_c1_bn_pool_fwd", B, D, H, W, C);
     if (rc) return rc;
-    static const int fwd_mult = getenv("TMF_C1_FWD_MULT") ? atoi(getenv("TMF_C1_FWD_MULT")) : 4;
-    const Plan p = make_plan(B, D, H, W, C, fwd_mult * SLAB_BLOCKS);     // a few bricks per workgroup (halo prefetch)
+    const Plan p = make_plan(B, D, H, W, C, tmf_opt(TMF_OPT_C1_FWD_MULT) * SLAB_BLOCKS);     // a few bricks per workgroup (halo prefetch)
     Args a = base_args(x, w, D, H, W, C, p, slope);
     a.scale = scale; a.shift = shift; a.pooled = pooled;
     TMF_REQUIRE(bf16 || !p16, TMF_E_ARG, "tmf_c1_bn_pool_fwd: bf16 tensors only with the bf16 kernels");

@@ -1604,11 +1604,12 @@ struct WgBfPlan { int tilesD, tilesH, tilesW, ntiles, gy, gz, tps, nsplit, nh; }
 // nh = 0: the register-transposing kernel (any channel counts); 1 / 2: the transposing-read kernel with 32 / 64 output
 // channels per workgroup (cin % 8 == 0 and cout % 8 == 0)
 int wgrad_tr_nh(int cin, int cout, int io) {
-    if (tmf_g_wgrad_tr == 0 || cin % 8 != 0 || cout % 8 != 0) return 0;
+    const int mode = tmf_opt(TMF_OPT_WGRAD_TR);
+    if (mode == 0 || cin % 8 != 0 || cout % 8 != 0) return 0;
     if (io) return cout > 32 ? 2 : 1;
     // fp32 tensors are rounded on the way and so staged through registers (32 output channels per workgroup): measured
     // ahead of the register-transposing kernel from 64 input channels on, level with it or behind below
-    return (cin >= 64 || tmf_g_wgrad_tr == 2) ? 1 : 0;
+    return (cin >= 64 || mode == 2) ? 1 : 0;
 }
 WgBfPlan plan_wgrad_bf16(int B, int D, int H, int W, int cin, int cout, int io) {
     WgBfPlan p;
@@ -1630,13 +1631,8 @@ WgBfPlan plan_wgrad_bf16(int B, int D, int H, int W, int cin, int cout, int io) 
 // slots reasonably; the choice depends on the geometry only (tmf_conv3d_bf16_stat_blocks has no channel arguments).
 // tmf_set_option("bf16_v2", 0) / TMF_BF_V2=0 selects the small-brick kernel everywhere, 2 the large-brick kernel
 // everywhere (A/B runs, tests), 1 (default) by the brick count.
-int tmf_g_debug = 0;             // tmf_set_option("debug", bits): timing ablations (results are garbage when set)
-int tmf_g_wgrad_tr = 1;          // tmf_set_option("wgrad_tr", 0 | 1 | 2)
-int tmf_g_bf16_dma = 1;          // tmf_set_option("bf16_dma", 0 | 1): LDS-DMA form of the 8x8x8-brick bf16 forward (bf16 tensors)
-int tmf_g_bf16_v2 = -1;          // tmf_set_option("bf16_v2", 0 | 1 | 2); -1 = not set yet: TMF_BF_V2 or 1
 static bool use_v2(int B, int D, int H, int W) {
-    if (tmf_g_bf16_v2 < 0) { const char* e = getenv("TMF_BF_V2"); tmf_g_bf16_v2 = e == nullptr ? 1 : atoi(e); }
-    const int mode = tmf_g_bf16_v2;
+    const int mode = tmf_opt(TMF_OPT_BF16_V2);
     if (mode == 0) return false;
     if (mode == 2) return true;
     return (long)B * tmf_cdiv(D, v2::TD) * tmf_cdiv(H, v2::TH) * tmf_cdiv(W, v2::TW) >= 384;
@@ -1666,10 +1662,9 @@ extern "C" const char* tmf_conv3d_fwd_bf16_kernel_name(int B, int D, int H, int 
     const char* o16 = (io & 2) ? "true" : "false";
     if (use_v2(B, D, H, W))
         snprintf(buf, sizeof buf, "conv3d_fwd_bf16_v2_kernel<%d, %s, %s, %s>", cout > 32 ? 2 : 1, i16, o16,
-                 ((io & 1) && tmf_g_bf16_dma) ? "true" : "false");
+                 ((io & 1) && tmf_opt(TMF_OPT_BF16_DMA)) ? "true" : "false");
     else {
-        static const bool nt2 = [] { const char* e = getenv("TMF_BF_NT2"); return e == nullptr || atoi(e) != 0; }();
-        snprintf(buf, sizeof buf, "conv3d_fwd_bf16_kernel<%d, %s, %s>", (nt2 && cout % 64 == 0) ? 2 : 1, i16, o16);
+        snprintf(buf, sizeof buf, "conv3d_fwd_bf16_kernel<%d, %s, %s>", (tmf_opt(TMF_OPT_BF_NT2) && cout % 64 == 0) ? 2 : 1, i16, o16);
     }
     return buf;
 }
@@ -1691,21 +1686,22 @@ extern "C" int tmf_conv3d_fwd_bf16_t(const void* x, const void* w_bf16, void* z,
     if (use_v2(B, D, H, W)) {
         const int tD = tmf_cdiv(D, v2::TD), tH = tmf_cdiv(H, v2::TH), tW = tmf_cdiv(W, v2::TW);
         const int ntiles = B * tD * tH * tW;
+        const int dma = tmf_opt(TMF_OPT_BF16_DMA), debug = tmf_opt(TMF_OPT_DEBUG);
 #define TMF_BF2_LAUNCH(NT, I16, O16, DMA_)                                                                           \
     do {                                                                                                             \
         auto k = conv3d_fwd_bf16_v2_kernel<NT, I16, O16, DMA_>;                                                      \
         const size_t ldsb = DMA_ ? v2::Cfg<NT>::LDS_BYTES_DMA : v2::Cfg<NT>::LDS_BYTES;                              \
         if ((rc = tmf_allow_lds(k, ldsb, "tmf_conv3d_fwd_bf16"))) return rc;                                         \
         hipLaunchKernelGGL(k, dim3(ntiles, tmf_cdiv(cout, 32 * NT)), dim3(v2::NTHR), ldsb, s, x,                      \
-                           (const u16*)w_bf16, z, stat_partial, D, H, W, cin, cout, tD, tH, tW, ntiles, tmf_g_debug); \
+                           (const u16*)w_bf16, z, stat_partial, D, H, W, cin, cout, tD, tH, tW, ntiles, debug);      \
     } while (0)
 #define TMF_BF2_IO(NT)                                                                                               \
     do {                                                                                                             \
         if (io == 0) TMF_BF2_LAUNCH(NT, false, false, false);                                                        \
-        else if (io == 1 && tmf_g_bf16_dma) TMF_BF2_LAUNCH(NT, true, false, true);                                   \
+        else if (io == 1 && dma) TMF_BF2_LAUNCH(NT, true, false, true);                                              \
         else if (io == 1) TMF_BF2_LAUNCH(NT, true, false, false);                                                    \
         else if (io == 2) TMF_BF2_LAUNCH(NT, false, true, false);                                                    \
-        else if (tmf_g_bf16_dma) TMF_BF2_LAUNCH(NT, true, true, true);                                               \
+        else if (dma) TMF_BF2_LAUNCH(NT, true, true, true);                                                          \
         else TMF_BF2_LAUNCH(NT, true, true, false);                                                                  \
     } while (0)
         if (cout > 32) TMF_BF2_IO(2);
@@ -1720,8 +1716,7 @@ extern "C" int tmf_conv3d_fwd_bf16_t(const void* x, const void* w_bf16, void* z,
     // the workgroups (the per-workgroup overhead — offsets, LDS writes, 9 barriers per chunk, epilogue — is 40 % of this
     // kernel), half the halo loads, one A fragment per two MFMAs; both variants stay under 128 registers / 80 KB, two
     // workgroups per CU.  -20 % per launch (conv2.3 at 64^3, bf16 tensors: 0.395 -> 0.317 ms).
-    static const bool nt2 = [] { const char* e = getenv("TMF_BF_NT2"); return e == nullptr || atoi(e) != 0; }();
-    const bool two = nt2 && cout % 64 == 0;
+    const bool two = tmf_opt(TMF_OPT_BF_NT2) && cout % 64 == 0;
 #define TMF_BF_LAUNCH(I16, O16)                                                                                      \
     if (two) {                                                                                                       \
         auto k = conv3d_fwd_bf16_kernel<2, I16, O16>;                                                                \

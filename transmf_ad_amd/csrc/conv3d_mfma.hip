@@ -874,24 +874,7 @@ template <int KS, int CINC> using CfgM64 = FwdCfg<KS, CINC, 1, 2, 4, 1, 4, 4, 8,
 // (no 27/32 round), but the two encoder streams of a train step already fill those rounds with each other's kernels —
 // model_ad steps at 14.75 ms either way; what has ONE stream gains (model_single, B = 16: 13.73 -> 13.59 ms; model_ad
 // with TMF_STREAMS=1: 15.84 -> 15.37).  DESIGN.md 3.1.
-int g_conv_rt = -1;
-int conv_rt() {
-    if (g_conv_rt < 0) {
-        const char* e = getenv("TMF_CONV_RT");
-        g_conv_rt = e == nullptr ? 0 : (atoi(e) == 2 ? 2 : (atoi(e) == 1 ? 1 : 0));
-    }
-    return g_conv_rt;
-}
-int g_debug = 0;          // timing ablations only (tmf_set_option("debug", bits)); results are garbage when set
-int g_conv_waves = 0;
-int conv_waves() {
-    if (g_conv_waves == 0) {
-        const char* e = getenv("TMF_CONV_WAVES");
-        const int v = e ? atoi(e) : 0;
-        g_conv_waves = (v == 4 || v == 2 || v == 8) ? v : 16;
-    }
-    return g_conv_waves;
-}
+int conv_waves() { return tmf_opt(TMF_OPT_CONV_WAVES); }
 
 struct FwdPlan {
     int cfg;      // 0 = L32, 1 = L64, 2 = S128  (+3: 8-wave variant); 6 = M32, 7 = M64
@@ -906,7 +889,8 @@ FwdPlan plan_fwd(int B, int D, int H, int W, int cin, int cout, int ks, bool all
     // Taken for the pooled volumes (<= 24^3 voxels per sample: +9 % over the ring kernel at 24^3 and 12^3, B = 8, measured per
     // layer with tools/conv_ab.py --opt conv_rt); at 48^3 the ring kernel's last round is 3/8 full and cheap, and its
     // 0.81-0.86 stands against 0.79-0.81 here.  tmf_set_option("conv_rt", 2) takes this form wherever its bricks fit.
-    const int rt_mode = conv_rt() > rt_min ? conv_rt() : rt_min;       // rt_min: the caller's per-call request (TMF_SNET_ALONE)
+    const int rt_opt = tmf_opt(TMF_OPT_CONV_RT);
+    const int rt_mode = rt_opt > rt_min ? rt_opt : rt_min;             // rt_min: the caller's per-call request (TMF_SNET_ALONE)
     const bool rt_size = rt_mode == 2 || (long)D * H * W <= 24L * 24 * 24;
     if (allow_rt && rt_mode && rt_size && ks == 3 && cin % 16 == 0 && cout % 16 == 0 && D % 6 == 0 && H % 6 == 0 && W % 12 == 0) {
         p.tilesD = D / 6; p.tilesH = H / 6; p.tilesW = W / 12;
@@ -932,7 +916,7 @@ FwdPlan plan_fwd(int B, int D, int H, int W, int cin, int cout, int ks, bool all
     // multiple of 4 instead of 8: 1 008 workgroups = 4 half units (conv3.0 at that size: 0.31 -> 0.22 ms; conv3.3 0.51 ->
     // 0.44, the model says 5 -> 4.3).  Chosen per launch by that model, the established brick on a tie; TMF_CONV_AUTO=0
     // keeps the 8-wave brick everywhere.
-    static const bool auto_brick = [] { const char* e = getenv("TMF_CONV_AUTO"); return e == nullptr || atoi(e) != 0; }();
+    const bool auto_brick = tmf_opt(TMF_OPT_CONV_AUTO);
     bool half_brick = false;
     if (auto_brick && ks == 3 && p.cinc == 32 && conv_waves() == 16 && p.cfg < 2) {
         const long nby = tmf_cdiv(cout, nb);
@@ -981,12 +965,12 @@ int launch_fwd_cfg(const FwdPlan& p, const float* x, const float* w, float* z, f
         auto k = conv3d_fwd_kernel<C, true, false>;
         if ((rc = tmf_allow_lds(k, C::LDS_BYTES, "tmf_conv3d_fwd"))) return rc;
         hipLaunchKernelGGL(k, grid, block, C::LDS_BYTES, s, x, w, z, sp, D, H, W, cin, cout,
-                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, g_debug, (const float*)nullptr, (const float*)nullptr, 0.f, 0);
+                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, tmf_opt(TMF_OPT_DEBUG), (const float*)nullptr, (const float*)nullptr, 0.f, 0);
     } else {
         auto k = conv3d_fwd_kernel<C, false, false>;
         if ((rc = tmf_allow_lds(k, C::LDS_BYTES, "tmf_conv3d_fwd"))) return rc;
         hipLaunchKernelGGL(k, grid, block, C::LDS_BYTES, s, x, w, z, sp, D, H, W, cin, cout,
-                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, g_debug, (const float*)nullptr, (const float*)nullptr, 0.f, 0);
+                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, tmf_opt(TMF_OPT_DEBUG), (const float*)nullptr, (const float*)nullptr, 0.f, 0);
     }
     return tmf_launch_result("tmf_conv3d_fwd");
 }
@@ -1641,61 +1625,6 @@ C1Plan plan_c1(int B, int D, int H, int W, int cout) {
 // ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
-static thread_local int t_algo_override = 0;
-int tmf_algo_override(void) { return t_algo_override; }
-void tmf_algo_override_set(int flags) { t_algo_override = (flags & TMF_SNET_ALGO) ? flags : 0; }
-int tmf_c1_gram_mode(void);      // conv1_gram.hip
-extern "C" int tmf_snet_algo_flags(void) {
-    return TMF_SNET_ALGO | TMF_SNET_ALGO_WINO(tmf_conv_wino_mode()) | (tmf_wino_p_mode() ? TMF_SNET_ALGO_WINO_P : 0) |
-           (tmf_wino_x_mode() ? TMF_SNET_ALGO_WINO_X : 0) | (tmf_c1_gram_mode() ? TMF_SNET_ALGO_C1_GRAM : 0) |
-           (tmf_c1_gram_mode() == 2 ? TMF_SNET_ALGO_C1_GRAM_BF16 : 0) | (tmf_c1_split_mode() ? TMF_SNET_ALGO_C1_SPLIT : 0);
-}
-
-extern "C" int tmf_set_option(const char* name, int value) {
-    TMF_REQUIRE_PTR(name);
-    if (strcmp(name, "conv_waves") == 0) {
-        TMF_REQUIRE(value == 4 || value == 8 || value == 2 || value == 16, TMF_E_ARG,
-                    "tmf_set_option: conv_waves must be 2, 4, 8 or 16, got %d", value);
-        g_conv_waves = value;
-        return TMF_OK;
-    }
-    if (strcmp(name, "conv_rt") == 0) {
-        TMF_REQUIRE(value >= 0 && value <= 2, TMF_E_ARG, "tmf_set_option: conv_rt must be 0, 1 or 2, got %d", value);
-        g_conv_rt = value;
-        return TMF_OK;
-    }
-    if (strcmp(name, "wino_p") == 0) return tmf_wino_p_set(value);
-    if (strcmp(name, "wino_x") == 0) return tmf_wino_x_set(value);
-    if (strcmp(name, "wino_cus") == 0) {
-        TMF_REQUIRE(value >= 0, TMF_E_ARG, "tmf_set_option: wino_cus must be >= 0, got %d", value);
-        return tmf_wino_cus_set(value);
-    }
-    if (strcmp(name, "c1_gram") == 0) return tmf_c1_gram_set(value);
-    if (strcmp(name, "c1_split") == 0) return tmf_c1_split_set(value);
-    if (strcmp(name, "conv_wino") == 0) {
-        TMF_REQUIRE(value >= 0 && value <= 3, TMF_E_ARG, "tmf_set_option: conv_wino must be 0, 1, 2 or 3, got %d", value);
-        return tmf_conv_wino_set(value);
-    }
-    if (strcmp(name, "debug") == 0) { g_debug = value; tmf_g_debug = value; return TMF_OK; }
-    if (strcmp(name, "bf16_v2") == 0) {
-        TMF_REQUIRE(value >= 0 && value <= 2, TMF_E_ARG, "tmf_set_option: bf16_v2 must be 0, 1 or 2, got %d", value);
-        tmf_g_bf16_v2 = value;
-        return TMF_OK;
-    }
-    if (strcmp(name, "bf16_dma") == 0) {
-        TMF_REQUIRE(value == 0 || value == 1, TMF_E_ARG, "tmf_set_option: bf16_dma must be 0 or 1, got %d", value);
-        tmf_g_bf16_dma = value;
-        return TMF_OK;
-    }
-    if (strcmp(name, "wgrad_tr") == 0) {
-        TMF_REQUIRE(value >= 0 && value <= 2, TMF_E_ARG, "tmf_set_option: wgrad_tr must be 0, 1 or 2, got %d", value);
-        tmf_g_wgrad_tr = value;
-        return TMF_OK;
-    }
-    tmf_set_error("tmf_set_option: unknown option '%s'", name);
-    return TMF_E_ARG;
-}
-
 extern "C" const char* tmf_conv3d_fwd_kernel_name(int B, int D, int H, int W, int cin, int cout, int ksize) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || (ksize != 1 && ksize != 3)) return "?";
     const FwdPlan p = plan_fwd(B, D, H, W, cin, cout, ksize);
@@ -1804,7 +1733,7 @@ extern "C" int tmf_conv3d_wgrad(const float* x, const float* dz, float* dw, void
         auto k = conv3d_wgrad_kernel<CFG, V>;                                                       \
         if ((rc = tmf_allow_lds(k, CFG::LDS_BYTES, "tmf_conv3d_wgrad"))) return rc;                 \
         hipLaunchKernelGGL(k, grid, dim3(CFG::NTHR), CFG::LDS_BYTES, s, x, dz, partial, D, H, W, cin, cout,   \
-                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, p.tps, g_debug);                 \
+                           p.tilesD, p.tilesH, p.tilesW, p.ntiles, p.tps, tmf_opt(TMF_OPT_DEBUG));  \
     } while (0)
         using L1 = WgCfg<1, 4, 8, 8>;
         using L2 = WgCfg<2, 4, 8, 8>;

@@ -35,7 +35,6 @@
 // same tolerances as the direct path.
 //
 // Replaces aten::conv3d / convolution_backward at /root/reference/models/networks.py:28,31,37,40,46.
-#include <atomic>
 #include <type_traits>
 #include "tmf_common.h"
 
@@ -1793,22 +1792,10 @@ __global__ __launch_bounds__(256) void wino_pack_multi_kernel(WinoPackMulti a) {
     wino_pack_layer(a.w[l], a.fwd[l], a.dgrad[l], a.cout[l], a.cin[l], blockIdx.x * 256 + threadIdx.x);
 }
 
-int g_conv_wino = -1;
-int g_wino_p = -1;          // forward / data gradient: 1 the persistent one-wave-per-SIMD kernel (default), 0 the two-waves-per-SIMD one
+// forward / data gradient: 1 the persistent one-wave-per-SIMD kernel (default), 0 the two-waves-per-SIMD one
+int wino_p_mode() { return tmf_opt(TMF_OPT_WINO_P); }
 
-int wino_p_mode() {
-    if (const int o = tmf_algo_override()) return (o & TMF_SNET_ALGO_WINO_P) ? 1 : 0;
-    if (g_wino_p < 0) {
-        const char* e = getenv("TMF_WINO_P");
-        g_wino_p = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    return g_wino_p;
-}
-
-// tmf_set_option("wino_cus", n): n > 0 caps the persistent workgroups (and statistic rows) at min(n, compute units), 0 = the device's
-// count or TMF_WINO_CUS.  Process-wide, read before the per-thread cache of the device's count.
-std::atomic<int> g_wino_cus{0};
-
+// "wino_cus" n > 0 caps the persistent workgroups (and statistic rows) at min(n, compute units); the device's count is cached per thread
 int wino_cu_count() {
     static thread_local int n[16] = {};
     int dev = 0;
@@ -1819,11 +1806,7 @@ int wino_cu_count() {
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         n[dev] = v;
     }
-    int cap = g_wino_cus.load(std::memory_order_relaxed);
-    if (cap <= 0) {
-        static const int env = getenv("TMF_WINO_CUS") ? atoi(getenv("TMF_WINO_CUS")) : 0;   // experiments: fewer persistent workgroups than compute units
-        cap = env;
-    }
+    const int cap = tmf_opt(TMF_OPT_WINO_CUS);
     return cap > 0 && cap < n[dev] ? cap : n[dev];
 }
 
@@ -1874,8 +1857,7 @@ int launch_wino_p_g(const char* what, const float* x, const float* u, float* z, 
         // as many workgroups as the launch needs for its number of ROUNDS (864 items on 256 CUs are 4 rounds: 216 workgroups
         // of exactly 4 items take as long as 256 of 3 or 4 and leave 40 CUs to the other encoder's stream)
         int grid = (int)(n < ncu ? n : ncu);
-        static const bool even = !(getenv("TMF_WINO_EVEN") && atoi(getenv("TMF_WINO_EVEN")) == 0);
-        if (even && n > ncu) {
+        if (tmf_opt(TMF_OPT_WINO_EVEN) && n > ncu) {
             const long rounds = (n + ncu - 1) / ncu;
             grid = (int)((n + rounds - 1) / rounds);
         }
@@ -1899,10 +1881,6 @@ int launch_wino_p(const char* what, const float* x, const float* u, float* z, fl
 
 }  // namespace
 
-int tmf_wino_p_set(int v) { g_wino_p = v ? 1 : 0; return TMF_OK; }
-int tmf_wino_cus_set(int v) { g_wino_cus.store(v, std::memory_order_relaxed); return TMF_OK; }
-extern "C" int tmf_wino_p_mode(void) { return wino_p_mode(); }
-
 #ifdef TMF_WINO_TRACE
 extern "C" int tmf_wino_trace_read(long long* blocks, long long* phases) {
     hipError_t e = hipMemcpyFromSymbol(blocks, HIP_SYMBOL(g_wino_blocks), sizeof(long long) * 8192 * 4);
@@ -1910,20 +1888,6 @@ extern "C" int tmf_wino_trace_read(long long* blocks, long long* phases) {
     return (int)e;
 }
 #endif
-
-// tmf_set_option("conv_wino", 0 | 1 | 2 | 3) / TMF_CONV_WINO: the Winograd form never / for the data gradients / for forward and
-// data gradients / (default) for forward, data and weight gradients of the encoder's 3x3x3 blocks that qualify (tmf_conv3d_wino_ok); consulted by the whole-encoder entries
-// (snet_path.hip) and, through tmf_conv_wino_mode(), by the op-by-op path (ops.py)
-extern "C" int tmf_conv_wino_mode(void) {
-    if (const int o = tmf_algo_override()) return (o >> 9) & 3;
-    if (g_conv_wino < 0) {
-        const char* e = getenv("TMF_CONV_WINO");
-        const int v = e ? atoi(e) : 3;
-        g_conv_wino = (v >= 0 && v <= 2) ? v : 3;
-    }
-    return g_conv_wino;
-}
-int tmf_conv_wino_set(int v) { g_conv_wino = v; return TMF_OK; }
 
 extern "C" int tmf_conv3d_wino_ok(int cin, int cout) { return cin > 0 && cout > 0 && cin % 8 == 0 && cout % 32 == 0; }
 

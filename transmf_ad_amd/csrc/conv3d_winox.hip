@@ -638,34 +638,17 @@ extern "C" int tmf_winox_trace_read(long long* phases) {
     return (int)hipMemcpyFromSymbol(phases, HIP_SYMBOL(g_winox_phases), sizeof(long long) * 8 * 64);
 }
 #endif
-namespace {
-int g_wino_x = -1;
-int wino_x_mode() {
-    if (const int o = tmf_algo_override()) return (o & TMF_SNET_ALGO_WINO_X) ? 1 : 0;
-    if (g_wino_x < 0) {
-        const char* e = getenv("TMF_WINO_X");
-        g_wino_x = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    return g_wino_x;
-}
-
-}  // namespace
-
-int tmf_wino_x_set(int v) { g_wino_x = v ? 1 : 0; return TMF_OK; }
-extern "C" int tmf_wino_x_mode(void) { return wino_x_mode(); }
-
 // does the split kernel take this launch?  (4x8x8 bricks of one sample only: the folded four-sample geometry of the small deep
 // volumes stays on the fp32 kernel; two 8-channel buffers per chunk and an even chunk count: cin % 32 == 0)
 int tmf_winox_takes(int B, int D, int H, int W, int cin, int cout, int geom) {
-    return wino_x_mode() && geom == 0 && cin % 32 == 0 && cout % 32 == 0 && cout <= 1024;
+    return tmf_opt(TMF_OPT_WINO_X) && geom == 0 && cin % 32 == 0 && cout % 32 == 0 && cout <= 1024;
 }
 
 // items per sample of a volume, and whether the transposed form (4-voxel side along the tensor's h) has fewer
 long tmf_winox_items(int D, int H, int W, int* swap) {
     const long t_n = (long)tmf_cdiv(D, BD) * tmf_cdiv(H, BH) * tmf_cdiv(W, BW);
     const long t_s = (long)tmf_cdiv(H, BD) * tmf_cdiv(D, BH) * tmf_cdiv(W, BW);
-    static const bool allow = !(getenv("TMF_WINOX_SWAP") && atoi(getenv("TMF_WINOX_SWAP")) == 0);
-    const int sw = allow && t_s < t_n ? 1 : 0;
+    const int sw = tmf_opt(TMF_OPT_WINOX_SWAP) && t_s < t_n ? 1 : 0;
     if (swap) *swap = sw;
     return sw ? t_s : t_n;
 }

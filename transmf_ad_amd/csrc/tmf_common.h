@@ -82,36 +82,33 @@ template <> struct TmfIO<tmf_bf16_t, 1> {
 #endif
 
 void tmf_set_error(const char* fmt, ...);
-extern int tmf_g_debug;          // conv3d_bf16.hip: timing-ablation bits (tmf_set_option("debug", ..))
-extern int tmf_g_wgrad_tr;       // conv3d_bf16.hip: bf16 weight-gradient kernel choice, tmf_set_option("wgrad_tr", 0 never | 1 where faster | 2 wherever possible: the transposing-read kernel)
 // conv3d_mfma.hip: tmf_conv3d_fwd / tmf_conv3d_stat_blocks with a per-call minimum for the "conv_rt" mode (snet_path.hip: TMF_SNET_ALONE)
 int tmf_conv3d_fwd_mode(const float* x, const float* w, float* z, float* stat_partial, int B, int D, int H, int W, int cin,
                         int cout, int ksize, int rt_min, void* stream);
 int tmf_conv3d_stat_blocks_mode(int B, int D, int H, int W, int cin, int cout, int ksize, int rt_min);
-int tmf_c1_split_set(int v);     // conv1_fused.hip: tmf_set_option("c1_split", 0 | 1): z of the first block (fp32) as exact 3-way bf16 splits
-int tmf_c1_gram_set(int v);      // conv1_gram.hip: tmf_set_option("c1_gram", 0 | 1): the first block through the tap Gram matrix of its input
-int tmf_wino_p_set(int v);       // conv3d_wino.hip: tmf_set_option("wino_p", 0 | 1): two-waves-per-SIMD / persistent one-wave-per-SIMD forward kernel
-int tmf_wino_cus_set(int v);     // conv3d_wino.hip: tmf_set_option("wino_cus", n): persistent Winograd workgroups capped at min(n, compute units), 0 = device / TMF_WINO_CUS
-// per-call algorithm choice (tmf_snet_desc.flags & TMF_SNET_ALGO): the whole-encoder entries set it for the calling thread while they
-// plan and enqueue; the option getters (tmf_conv_wino_mode, wino_p_mode, wino_x_mode, c1_gram_mode) look here first
-int  tmf_algo_override(void);            // 0, or a flags word with TMF_SNET_ALGO set
-void tmf_algo_override_set(int flags);
-struct TmfAlgoScope {
+// Process options (options.hip: one table row each; include/tmf_hip.h documents them).  tmf_opt: the value in effect — the
+// calling entry's choice for the options of the per-call word (below), else tmf_set_option's, else the environment's, else the default.
+enum TmfOpt {
+    TMF_OPT_CONV_WINO, TMF_OPT_WINO_P, TMF_OPT_WINO_X, TMF_OPT_C1_GRAM, TMF_OPT_C1_SPLIT,       // (also per call)
+    TMF_OPT_WINO_CUS, TMF_OPT_CONV_RT, TMF_OPT_CONV_WAVES, TMF_OPT_BF16_V2, TMF_OPT_BF16_DMA, TMF_OPT_WGRAD_TR, TMF_OPT_DEBUG,
+    TMF_OPT_WINO_EVEN, TMF_OPT_WINOX_SWAP, TMF_OPT_BF_NT2, TMF_OPT_CONV_AUTO, TMF_OPT_C1_BLOCKS, TMF_OPT_C1_FWD_MULT,   // (environment only)
+    TMF_OPT_COUNT
+};
+int tmf_opt(TmfOpt o);
+// per-call algorithm choice (tmf_snet_desc.flags & TMF_SNET_ALGO): the whole-encoder entries hold it for the calling thread while they
+// plan and enqueue (a word without TMF_SNET_ALGO keeps the one held before); tmf_opt decodes it for the options it carries
+struct TmfAlgoScope {       // options.hip
     int prev;
-    explicit TmfAlgoScope(int flags) : prev(tmf_algo_override()) { if (flags & TMF_SNET_ALGO) tmf_algo_override_set(flags); }
-    ~TmfAlgoScope() { tmf_algo_override_set(prev); }
+    explicit TmfAlgoScope(int flags);
+    ~TmfAlgoScope();
     TmfAlgoScope(const TmfAlgoScope&) = delete;
     TmfAlgoScope& operator=(const TmfAlgoScope&) = delete;
 };
-int tmf_wino_x_set(int v);       // conv3d_winox.hip: tmf_set_option("wino_x", 0 | 1): Winograd forward / data gradient as exact 3-way bf16 splits on the bf16 matrix pipe
 int tmf_winox_takes(int B, int D, int H, int W, int cin, int cout, int geom);
 long tmf_winox_items(int D, int H, int W, int* swap);     // items per sample (the better of the two item orientations)
 int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3, float* z, float* stat_partial, int B, int D, int H,
                      int W, int cin, int cout, int ncu, hipStream_t stream, const float* scale = nullptr, const float* shift = nullptr,
                      float slope = 0.f, int pool = 0);     // scale != NULL: the eval-mode block (y = LeakyReLU(scale z + shift), pool none | max)
-int tmf_conv_wino_set(int v);    // conv3d_wino.hip: tmf_set_option("conv_wino", 0 | 1 | 2)
-extern int tmf_g_bf16_dma;       // conv3d_bf16.hip: LDS-DMA form of the large-brick bf16 forward kernel (tmf_set_option("bf16_dma", 0 | 1))
-extern int tmf_g_bf16_v2;        // conv3d_bf16.hip: kernel choice of the bf16 forward (tmf_set_option("bf16_v2", ..))
 
 #define TMF_REQUIRE_PTR(p)                                                     \
     do {                                                                       \
