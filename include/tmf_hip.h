@@ -358,6 +358,13 @@ int tmf_layernorm_bwd_blocks(int rows, int dim);
 /* partial: [nblk][2][dim] (dgamma, dbeta partials; reduce with tmf_colsum_finalize, ncol = 2*dim). */
 int tmf_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd,
                       const float* dy, float* dx, float* partial, int rows, int dim, void* stream);
+/* The same, and also dx_masked = dx * mask (mask [rows][dim]: a Dropout keep-mask already scaled by 1 / (1 - p)) in the
+ * same pass: the block-final LayerNorm's input gradient and its m_f-masked copy (networks.py:133). */
+int tmf_layernorm_bwd_masked(const float* x, const float* gamma, const float* mean, const float* rstd,
+                             const float* dy, float* dx, float* partial, int rows, int dim,
+                             const float* mask, float* dx_masked, void* stream);
+/* y = x * mask over n floats (16-byte aligned): a keep-mask applied to a gradient no other entry produces. */
+int tmf_mask_mul(const float* x, const float* mask, float* y, long n, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Linear layers of the fusion transformer fused with their neighbours (token_gemm.hip): one launch per
@@ -386,6 +393,20 @@ int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* dx, int R, 
                              const float* gelu_pre, const float* ln_x, const float* ln_mean, const float* ln_rstd,
                              const float* ln_gamma, const float* add1, const float* add2, float* ln_partial,
                              float* bias_partial, int partial_stride, void* stream);
+/* Dropout forms (networks.py:131,133,153), same shapes and checks; mask: a keep-mask already scaled by 1 / (1 - p), never NULL.
+ * forward:  y = (..) . w^T + bias,  then  y = y * mask [+ residual]   or, gelu_pre != NULL,  y = GELU(gelu_pre) * mask
+ *   (gelu_pre itself unmasked); mask [R][Nout].
+ * backward (mask [R][K]): exactly one of
+ *   gelu_pre != NULL: dx = (dy . w) * mask * GELU'(gelu_pre)   (no add1 / add2 / dx_masked);
+ *   ln_x != NULL:     dx as in tmf_tok_linear_bwd_input's LayerNorm-backward epilogue, and dx_masked = dx * mask. */
+int tmf_tok_linear_fwd_masked(const float* x, const float* w, const float* bias, const float* residual, float* y,
+                              int R, int K, int Nout, const float* ln_gamma, const float* ln_beta, float eps,
+                              float* ln_mean, float* ln_rstd, float* ln_out, float* gelu_pre, const float* mask, void* stream);
+int tmf_tok_linear_bwd_input_masked(const float* dy, const float* w, float* dx, int R, int Nout, int K,
+                                    const float* gelu_pre, const float* ln_x, const float* ln_mean, const float* ln_rstd,
+                                    const float* ln_gamma, const float* add1, const float* add2, float* ln_partial,
+                                    float* bias_partial, int partial_stride, const float* mask, float* dx_masked,
+                                    void* stream);
 
 /* Conv weights from the reference layout (Cout, Cin, k, k, k) of nn.Conv3d (networks.py:22,28,31,37,40,46,49;
  * taps = k^3 = 1 | 27) into the forward / weight-gradient
@@ -549,8 +570,8 @@ int    tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const tmf_sne
  * forward, or of its backward.  Replaces `self.fuse_transformer(mri_embeddings, pet_embeddings)` (models/mymodel.py:220
  * -> networks.py:272-281: depth x [mri <- Transformer(mri | pet) + mri; pet <- Transformer(pet | NEW mri) + pet], then
  * cat[mean, mean, max, max] over tokens) and its slice of `all_loss.backward()`.  Dropout (options/option.py:39) enters as
- * keep-masks in tmf_xformer_params.  dim of 64, 128 or 256; heads*dim_head and mlp multiples of 64.  Dims other than
- * 128 always run one launch per op, and take no keep-masks.
+ * keep-masks in tmf_xformer_params, at every descriptor the entries accept (tmf_fusion_takes_masks).  dim of 64, 128 or
+ * 256; heads*dim_head and mlp multiples of 64.  Dims other than 128 always run one launch per op.
  *
  * inst[2*l] / inst[2*l + 1] = the mri / pet Transformer(depth=1) of layer l, parameters = the reference's state_dict
  * tensors (nn.Linear weights (out, in)).  Gradients: small = [b2 (dim) | b1 (mlp) | bo (dim) | ln2 gamma | ln2 beta |
@@ -573,7 +594,8 @@ typedef struct tmf_xformer_params {
     float eps1, eps2, epsf;
     /* Dropout keep-masks of the instance ALREADY scaled by 1 / (1 - p), or NULL (eval, or p = 0): after to_out
      * (networks.py:153) [B*N][dim], after GELU (:131) [B*N][mlp], after the second Linear (:133) [B*N][dim].  The random
-     * draw stays with the caller; the same pointers must be passed to forward and backward.  Fused kernels only. */
+     * draw stays with the caller; the same pointers must be passed to forward and backward.  The fused kernels apply them
+     * in their own epilogues, one launch per op in the masked token-GEMM / LayerNorm-backward instances. */
     const float *mask_o, *mask_g, *mask_f;
 } tmf_xformer_params;
 typedef struct tmf_xformer_grads {
@@ -584,6 +606,9 @@ typedef struct tmf_xformer_grads {
 void   tmf_debug_xf_trace(void* fwd, void* bwd_q, void* bwd_kv);
 size_t tmf_fusion_saved_bytes(const tmf_fusion_desc* d);
 int    tmf_fusion_uses_fused(const tmf_fusion_desc* d);     /* 1: this descriptor's calls run the fused per-instance kernels */
+int    tmf_fusion_takes_masks(const tmf_fusion_desc* d);    /* 1: this descriptor's calls take keep-masks (all it accepts) */
+/* One launch per op (tmf_fusion_uses_fused = 0) always reserves room for the two masked gradients m_f * dx2, m_o * dx1
+ * (2 B N dim floats), masks or not: the descriptor does not say whether masks come. */
 size_t tmf_fusion_bwd_scratch_bytes(const tmf_fusion_desc* d);
 int    tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
                             const tmf_xformer_params* inst, void* saved, size_t saved_bytes, float* cls, void* stream);

@@ -10,7 +10,10 @@ Adam) — with the fusion block on each of its three paths:
 Every (dim, setting) runs as a fresh child process under its own `timeout`, the settings in alternating order per round;
 each child prints one JSON line (ms per step, pairs/s, the path its fusion block took, its F.linear calls per step).
 
-    python tools/dim_step.py [--dims 64 256] [--rounds 2] [--steps 30] [--warmup 10]
+    python tools/dim_step.py [--dims 64 256] [--rounds 2] [--steps 30] [--warmup 10] [--dropout P]
+
+--dropout P builds the model with the fusion block's Dropout at P (options/option.py:39); the default 0 is the
+dropout-free step.
 """
 import argparse
 import json
@@ -33,7 +36,7 @@ def child(args):
 
     B, dim, dev = args.batch, args.dim, "cuda"
     torch.manual_seed(0)
-    net = T.model_ad(dim=dim, depth=3, heads=4, dim_head=dim // 4, mlp_dim=4 * dim, dropout=0.).to(dev).train()
+    net = T.model_ad(dim=dim, depth=3, heads=4, dim_head=dim // 4, mlp_dim=4 * dim, dropout=args.dropout).to(dev).train()
     opt = Adam(net.parameters(), lr=1e-4)
     mri, pet = torch.rand(B, 1, 96, 96, 96, device=dev), torch.rand(B, 1, 96, 96, 96, device=dev)
     y = torch.arange(B, device=dev) % 2
@@ -79,7 +82,8 @@ def child(args):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     print(json.dumps(dict(dim=dim, setting=args.setting, ms_per_step=round(ms, 3), pairs_per_s=round(B / ms * 1e3, 1),
-                          path=path, f_linear_calls_per_step=n_lin[0], steps=args.steps, batch=B)), flush=True)
+                          path=path, f_linear_calls_per_step=n_lin[0], steps=args.steps, batch=B, dropout=args.dropout)),
+          flush=True)
 
 
 def parent(args):
@@ -91,7 +95,7 @@ def parent(args):
                 env = dict(os.environ, **SETTINGS[s])
                 cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child",
                        "--dim", str(dim), "--setting", s, "--steps", str(args.steps), "--warmup", str(args.warmup),
-                       "--batch", str(args.batch)]
+                       "--batch", str(args.batch), "--dropout", str(args.dropout)]
                 p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True)
                 if p.returncode != 0:
                     sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
@@ -117,6 +121,7 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--dropout", type=float, default=0.0, help="the fusion block's Dropout p (0: off)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child process")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--dim", type=int)

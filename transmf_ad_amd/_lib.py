@@ -112,6 +112,10 @@ PROTOTYPES = {
     "tmf_tok_linear_bwd_input": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     "tmf_layernorm_bwd_blocks": (_i, [_i, _i]),
     "tmf_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "tmf_tok_linear_fwd_masked": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
+    "tmf_tok_linear_bwd_input_masked": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "tmf_layernorm_bwd_masked": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "tmf_mask_mul": (_i, [_p, _p, _p, _l, _p]),
     "tmf_token_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "tmf_token_pool_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
 }
@@ -175,6 +179,7 @@ PROTOTYPES.update({
     "tmf_debug_xf_trace": (None, [_p, _p, _p]),
     "tmf_fusion_saved_bytes": (_z, [C.POINTER(FusionDesc)]),
     "tmf_fusion_uses_fused": (_i, [C.POINTER(FusionDesc)]),
+    "tmf_fusion_takes_masks": (_i, [C.POINTER(FusionDesc)]),
     "tmf_fusion_bwd_scratch_bytes": (_z, [C.POINTER(FusionDesc)]),
     "tmf_fusion_train_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
     "tmf_fusion_train_bwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p,

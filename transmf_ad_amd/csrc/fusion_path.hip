@@ -71,8 +71,8 @@ struct Plan {
     int npad, tiles;
     InstPlan I;                 // identical for every instance
     size_t off_arg, saved_bytes;
-    // backward scratch (byte offsets)
-    size_t s_dx2, s_dh, s_dx1, s_dout, s_dq, s_dkv, s_part, s_lnpart, s_G[4], s_ws, ws_bytes, scratch_bytes;
+    // backward scratch (byte offsets); s_ef / s_eo: one launch per op only, the Dropout-masked m_f * dx2 and m_o * dx1
+    size_t s_dx2, s_dh, s_dx1, s_dout, s_dq, s_dkv, s_part, s_lnpart, s_G[4], s_ws, ws_bytes, s_ef, s_eo, scratch_bytes;
     // fused backward: s_dx2 .. s_dkv and s_part are the first of `2 * depth` per-instance regions of inst_stride bytes
     size_t s_DR, s_DC, s_delta, inst_stride;
 };
@@ -135,6 +135,9 @@ Plan make_plan(const tmf_fusion_desc& d) {
     }
     if (p.ws_bytes < 16) p.ws_bytes = 16;
     p.s_ws = take(p.ws_bytes / 4 + 1);
+    // The descriptor does not say whether keep-masks come: one launch per op always reserves e_f and e_o (2 R dim floats)
+    p.s_ef = p.s_eo = 0;
+    if (!p.fused) { p.s_ef = take(R * dim); p.s_eo = take(R * dim); }
     p.scratch_bytes = o;
     return p;
 }
@@ -154,6 +157,12 @@ extern "C" int tmf_fusion_uses_fused(const tmf_fusion_desc* d) {
     return make_plan(*d).fused ? 1 : 0;
 }
 
+// 1: the calls of this descriptor take Dropout keep-masks — every descriptor they accept (the fused kernels apply them in
+// their own epilogues, one launch per op in token_gemm.hip's / token_ops.hip's masked instances)
+extern "C" int tmf_fusion_takes_masks(const tmf_fusion_desc* d) {
+    return check_desc("tmf_fusion_takes_masks", d) == TMF_OK ? 1 : 0;
+}
+
 extern "C" size_t tmf_fusion_bwd_scratch_bytes(const tmf_fusion_desc* d) {
     if (check_desc("tmf_fusion_bwd_scratch_bytes", d) != TMF_OK) return 0;
     return make_plan(*d).scratch_bytes;
@@ -171,12 +180,25 @@ static int instance_fwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
                                nullptr, nullptr, nullptr, stream));
     TMF_TRY(tmf_xattn_fwd(F(sv, I.q), F(sv, I.kv), F(sv, I.kv) + inner, F(sv, I.out), F(sv, I.lse), d.B, d.heads, d.N, d.N,
                           d.dim_head, inner, 2 * inner, scale, stream));
-    TMF_TRY(tmf_tok_linear_fwd(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr, nullptr,
-                               nullptr, nullptr, stream));
-    TMF_TRY(tmf_tok_linear_fwd(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2, F(sv, I.m2),
-                               F(sv, I.r2), F(sv, I.f), F(sv, I.h), stream));
-    TMF_TRY(tmf_tok_linear_fwd(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f, nullptr,
-                               nullptr, nullptr, nullptr, stream));
+    // Dropout (masks non-NULL): x1 = m_o (out Wo^T + bo) + x,  g = m_g GELU(h) with h unmasked,  x2 = m_f (g W2^T + b2) + x1
+    if (w.mask_o)
+        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr,
+                                          nullptr, nullptr, nullptr, w.mask_o, stream));
+    else
+        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr, nullptr,
+                                   nullptr, nullptr, stream));
+    if (w.mask_g)
+        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2,
+                                          F(sv, I.m2), F(sv, I.r2), F(sv, I.f), F(sv, I.h), w.mask_g, stream));
+    else
+        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2, F(sv, I.m2),
+                                   F(sv, I.r2), F(sv, I.f), F(sv, I.h), stream));
+    if (w.mask_f)
+        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f,
+                                          nullptr, nullptr, nullptr, nullptr, w.mask_f, stream));
+    else
+        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f, nullptr,
+                                   nullptr, nullptr, nullptr, stream));
     // block-final LayerNorm with the caller's "+ tokens" (networks.py:274-275) folded into the same pass
     TMF_TRY(tmf_layernorm_fwd(F(sv, I.x2), w.lnf_g, w.lnf_b, x, F(sv, I.y), F(sv, I.mf), F(sv, I.rf), R, dim, w.epsf, stream));
     return TMF_OK;
@@ -204,9 +226,6 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
     char* base = (char*)saved;
     const float* m = mri_tok;
     const float* q = pet_tok;
-    for (int i = 0; i < 2 * d->depth; ++i)
-        TMF_REQUIRE(p.fused || (!inst[i].mask_o && !inst[i].mask_g && !inst[i].mask_f), TMF_E_SHAPE,
-                    "tmf_fusion_train_fwd: Dropout masks need the fused kernels (dim 128, 4 heads of 32 or 8 of 16, mlp 512, N <= 512)");
     if (p.fused && d->depth > 0) {
         const float scale = 1.0f / sqrtf((float)d->dim_head);
         hipStream_t s = (hipStream_t)stream;
@@ -268,16 +287,35 @@ static int instance_bwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
           *dkv = F(sc, p.s_dkv), *part = F(sc, p.s_part), *lnpart = F(sc, p.s_lnpart);
     // small-parameter gradients share one [row blocks][stride] partial workspace; column order = g.small's layout
     const int o_b2 = 0, o_b1 = dim, o_bo = dim + mlp, o_ln2 = 2 * dim + mlp, o_ln1 = 4 * dim + mlp;
+    // Dropout: e_f = m_f dx2 and e_o = m_o dx1 are the dy of the FF2 / to_out Linears (dgrad, bias sums, weight gradients);
+    // the residual paths carry the unmasked dx2 / dx1.  Without a mask e_f = dx2, e_o = dx1.
+    float *ef = dx2, *eo = dx1;
     // block-final LayerNorm
-    TMF_TRY(tmf_layernorm_bwd(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, stream));
+    if (w.mask_f) {
+        ef = F(sc, p.s_ef);
+        TMF_TRY(tmf_layernorm_bwd_masked(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, w.mask_f, ef,
+                                         stream));
+    } else {
+        TMF_TRY(tmf_layernorm_bwd(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, stream));
+    }
     TMF_TRY(tmf_colsum_finalize(lnpart, p.nblk_ln, 2 * dim, g.lnf, stream));
     // FeedForward
-    TMF_TRY(tmf_tok_linear_bwd_input(dx2, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, part + o_b2, stride, stream));
-    TMF_TRY(tmf_tok_linear_bwd_input(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g, dx2,
-                                     nullptr, part + o_ln2, part + o_b1, stride, stream));
+    if (w.mask_g)
+        TMF_TRY(tmf_tok_linear_bwd_input_masked(ef, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                nullptr, nullptr, part + o_b2, stride, w.mask_g, nullptr, stream));
+    else
+        TMF_TRY(tmf_tok_linear_bwd_input(ef, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, part + o_b2, stride, stream));
+    if (w.mask_o) {
+        eo = F(sc, p.s_eo);
+        TMF_TRY(tmf_tok_linear_bwd_input_masked(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g,
+                                                dx2, nullptr, part + o_ln2, part + o_b1, stride, w.mask_o, eo, stream));
+    } else {
+        TMF_TRY(tmf_tok_linear_bwd_input(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g, dx2,
+                                         nullptr, part + o_ln2, part + o_b1, stride, stream));
+    }
     // Attention
-    TMF_TRY(tmf_tok_linear_bwd_input(dx1, w.wo, dout, R, dim, inner, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    TMF_TRY(tmf_tok_linear_bwd_input(eo, w.wo, dout, R, dim, inner, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                      nullptr, part + o_bo, stride, stream));
     TMF_TRY(tmf_xattn_bwd(F(sv, I.q), F(sv, I.kv), F(sv, I.kv) + inner, F(sv, I.out), F(sv, I.lse), dout, dq, dkv, dkv + inner,
                           d.B, d.heads, d.N, d.N, d.dim_head, inner, 2 * inner, 2 * inner, scale, stream));
@@ -286,7 +324,7 @@ static int instance_bwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
     TMF_TRY(tmf_tok_linear_bwd_input(dq, w.wq, dx_out, R, inner, dim, nullptr, x, F(sv, I.m1), F(sv, I.r1), w.ln1_g, dx1, dy,
                                      part + o_ln1, nullptr, stride, stream));
     TMF_TRY(tmf_colsum_finalize(part, p.nblk, stride, g.small, stream));
-    const float* dys[5] = {dx2, dh, dx1, dkv, dq};
+    const float* dys[5] = {ef, dh, eo, dkv, dq};
     const float* xs[5] = {F(sv, I.g), F(sv, I.f), F(sv, I.out), c, F(sv, I.a)};
     float* dws[5] = {g.dw2, g.dw1, g.dwo, g.dwkv, g.dwq};
     const int Rs[5] = {R, R, R, R, R}, Ns[5] = {dim, mlp, dim, 2 * inner, inner}, Ks[5] = {mlp, dim, inner, dim, dim};

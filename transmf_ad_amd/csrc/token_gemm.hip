@@ -38,6 +38,8 @@ struct TokArgs {
     const float* lnb_x; const float* lnb_mean; const float* lnb_rstd; const float* lnb_g;
     const float* add1; const float* add2;
     float* lnb_partial; float* colsum_partial; int partial_stride;
+    // Dropout epilogues (the *_MASK instances only): keep-mask [R][N], already scaled by 1 / (1 - p); masked copy of Y
+    const float* mask; float* Y2;
 };
 
 __device__ __forceinline__ float gelu_f(float h) { return 0.5f * h * (1.f + erff(h * 0.70710678118654752f)); }
@@ -63,7 +65,12 @@ __device__ __forceinline__ f32x2 affine(f32x2 d, float rs, f32x2 g, f32x2 b) {
     return f32x2{d[0] * rs * g[0] + b[0], d[1] * rs * g[1] + b[1]};
 }
 
-enum { EPI_PLAIN = 0, EPI_GELU = 1, EPI_GELU_GRAD = 2, EPI_LN_BWD = 3 };
+enum { EPI_PLAIN = 0, EPI_GELU = 1, EPI_GELU_GRAD = 2, EPI_LN_BWD = 3,
+       // the same four with a Dropout keep-mask (p.mask [R][N]); instances of their own, the four above stay as they are
+       EPI_PLAIN_MASK = 4,          // forward   y = (acc + bias) * mask + residual           (to_out, FeedForward's 2nd Linear)
+       EPI_GELU_MASK = 5,           // forward   pre = acc + bias (unmasked), y = GELU(pre) * mask   (FeedForward's 1st)
+       EPI_GELU_GRAD_MASK = 6,      // backward  dx = acc * mask * GELU'(h)
+       EPI_LN_BWD_MASK = 7 };       // backward  dx as EPI_LN_BWD, and Y2 = dx * mask (the masked copy next to it)
 
 // LNK: row width of the LayerNorm prologue (64, 128 or 256), 0 = none.  CT: MFMA column tiles per wave.
 template <bool NN, int LNK, int EPI, int CT>
@@ -210,23 +217,28 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
     }
 
     // ---- epilogue.  D fragment: column = lane & 15, row = 4 * (lane >> 4) + r ----
-    if (EPI == EPI_PLAIN || EPI == EPI_GELU || EPI == EPI_GELU_GRAD) {
+    constexpr bool MASK = EPI >= EPI_PLAIN_MASK;
+    constexpr int E = MASK ? EPI - EPI_PLAIN_MASK : EPI;      // the epilogue without its keep-mask
+    if (E == EPI_PLAIN || E == EPI_GELU || E == EPI_GELU_GRAD) {
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
             const int col = c0 + t * 16 + m;
-            const float bv = (EPI != EPI_GELU_GRAD && p.bias != nullptr) ? p.bias[col] : 0.f;
+            const float bv = (E != EPI_GELU_GRAD && p.bias != nullptr) ? p.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int gr = r0 + 4 * kb + r;
                 if (gr < p.R) {
                     const size_t o = (size_t)gr * p.N + col;
                     float v = acc[t][r] + bv;
-                    if (EPI == EPI_PLAIN) {
+                    if (E == EPI_PLAIN) {
+                        if (MASK) v *= p.mask[o];
                         if (p.res != nullptr) v += p.res[o];
-                    } else if (EPI == EPI_GELU) {
+                    } else if (E == EPI_GELU) {
                         p.pre[o] = v;
                         v = gelu_f(v);
+                        if (MASK) v *= p.mask[o];
                     } else {
+                        if (MASK) v *= p.mask[o];
                         v *= gelu_grad_f(p.gelu_h[o]);
                     }
                     p.Y[o] = v;
@@ -289,6 +301,7 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
                     if (p.add1 != nullptr) v += p.add1[o];
                     if (p.add2 != nullptr) v += p.add2[o];
                     p.Y[o] = v;
+                    if (MASK) p.Y2[o] = v * p.mask[o];
                 }
             }
         }
@@ -380,6 +393,68 @@ extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* 
     a.res = add1;                                                    // plain epilogue: + add1 (one residual gradient)
     TMF_REQUIRE(add2 == nullptr, TMF_E_SHAPE, "tmf_tok_linear_bwd_input: add2 needs the LayerNorm epilogue");
     return launch_bwd<EPI_PLAIN>(a, s, "tmf_tok_linear_bwd_input");
+}
+
+// The Dropout forms of the two entries above: the same tiles and checks, the *_MASK epilogue instances.
+extern "C" int tmf_tok_linear_fwd_masked(const float* x, const float* w, const float* bias, const float* residual, float* y,
+                                         int R, int K, int Nout, const float* ln_gamma, const float* ln_beta, float eps,
+                                         float* ln_mean, float* ln_rstd, float* ln_out, float* gelu_pre, const float* mask,
+                                         void* stream) {
+    TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(y); TMF_REQUIRE_PTR(mask);
+    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_fwd_masked: non-positive dimension");
+    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % 64 == 0, TMF_E_SHAPE,
+                "tmf_tok_linear_fwd_masked: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 64", K, Nout);
+    TMF_REQUIRE(gelu_pre == nullptr || residual == nullptr, TMF_E_SHAPE,
+                "tmf_tok_linear_fwd_masked: GELU epilogue takes no residual");
+    TokArgs a = {};
+    a.A = x; a.W = w; a.Y = y; a.R = R; a.K = K; a.N = Nout;
+    a.bias = bias; a.res = residual; a.pre = gelu_pre; a.mask = mask;
+    hipStream_t s = (hipStream_t)stream;
+    const bool gelu = gelu_pre != nullptr;
+    if (ln_gamma != nullptr) {
+        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
+                    "tmf_tok_linear_fwd_masked: the LayerNorm prologue needs K of 64, 128 or 256 (got %d)", K);
+        TMF_REQUIRE_PTR(ln_beta); TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd);
+        a.ln_g = ln_gamma; a.ln_b = ln_beta; a.eps = eps; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_out = ln_out;
+        const char* what = gelu ? "tmf_tok_linear_fwd_masked(ln,gelu)" : "tmf_tok_linear_fwd_masked(ln)";
+        if (K == 64) return gelu ? launch_fwd<64, EPI_GELU_MASK>(a, s, what) : launch_fwd<64, EPI_PLAIN_MASK>(a, s, what);
+        if (K == 128) return gelu ? launch_fwd<128, EPI_GELU_MASK>(a, s, what) : launch_fwd<128, EPI_PLAIN_MASK>(a, s, what);
+        return gelu ? launch_fwd<256, EPI_GELU_MASK>(a, s, what) : launch_fwd<256, EPI_PLAIN_MASK>(a, s, what);
+    }
+    if (gelu) return launch_fwd<0, EPI_GELU_MASK>(a, s, "tmf_tok_linear_fwd_masked(gelu)");
+    return launch_fwd<0, EPI_PLAIN_MASK>(a, s, "tmf_tok_linear_fwd_masked");
+}
+
+extern "C" int tmf_tok_linear_bwd_input_masked(const float* dy, const float* w, float* dx, int R, int Nout, int K,
+                                               const float* gelu_pre, const float* ln_x, const float* ln_mean,
+                                               const float* ln_rstd, const float* ln_gamma, const float* add1,
+                                               const float* add2, float* ln_partial, float* bias_partial,
+                                               int partial_stride, const float* mask, float* dx_masked, void* stream) {
+    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(mask);
+    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_bwd_input_masked: non-positive dimension");
+    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % 64 == 0, TMF_E_SHAPE,
+                "tmf_tok_linear_bwd_input_masked: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 64", Nout, K);
+    TMF_REQUIRE((ln_partial == nullptr && bias_partial == nullptr) || partial_stride > 0, TMF_E_SHAPE,
+                "tmf_tok_linear_bwd_input_masked: partial_stride must be positive");
+    TMF_REQUIRE((gelu_pre != nullptr) != (ln_x != nullptr), TMF_E_SHAPE,
+                "tmf_tok_linear_bwd_input_masked: needs exactly one of the GELU-gradient and LayerNorm-backward epilogues");
+    TokArgs a = {};
+    a.A = dy; a.W = w; a.Y = dx; a.R = R; a.K = Nout; a.N = K;       // contraction over dy's columns
+    a.gelu_h = gelu_pre; a.add1 = add1; a.add2 = add2; a.mask = mask; a.Y2 = dx_masked;
+    a.lnb_partial = ln_partial; a.colsum_partial = bias_partial; a.partial_stride = partial_stride;
+    hipStream_t s = (hipStream_t)stream;
+    if (ln_x != nullptr) {
+        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
+                    "tmf_tok_linear_bwd_input_masked: the LayerNorm-backward epilogue needs K of 64, 128 or 256 (K=%d)", K);
+        TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd); TMF_REQUIRE_PTR(ln_gamma); TMF_REQUIRE_PTR(dx_masked);
+        a.lnb_x = ln_x; a.lnb_mean = ln_mean; a.lnb_rstd = ln_rstd; a.lnb_g = ln_gamma;
+        if (K == 64) return launch_tok<true, 0, EPI_LN_BWD_MASK, 1>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
+        if (K == 128) return launch_tok<true, 0, EPI_LN_BWD_MASK, 2>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
+        return launch_tok<true, 0, EPI_LN_BWD_MASK, 4>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
+    }
+    TMF_REQUIRE(add1 == nullptr && add2 == nullptr && dx_masked == nullptr, TMF_E_SHAPE,
+                "tmf_tok_linear_bwd_input_masked: the GELU-gradient epilogue takes no add1, add2 or dx_masked");
+    return launch_bwd<EPI_GELU_GRAD_MASK>(a, s, "tmf_tok_linear_bwd_input_masked(gelu)");
 }
 
 // ------------------------------------------------------------------------------------------------------------

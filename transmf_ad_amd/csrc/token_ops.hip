@@ -59,11 +59,13 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma
 // partial[blk][0][c] = sum_rows dy*xhat, partial[blk][1][c] = sum_rows dy
-template <int VEC>
+// MASK (instances of their own): also dxm = dx * mask (a Dropout keep-mask [rows][dim]) next to the unmasked dx
+template <int VEC, bool MASK = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ dy, float* __restrict__ dx,
-    float* __restrict__ partial, int rows, int dim, int rows_per_block) {
+    float* __restrict__ partial, int rows, int dim, int rows_per_block, const float* __restrict__ mask = nullptr,
+    float* __restrict__ dxm = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float red[];   // [4][2][dim]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float ag[LN_MAXV * VEC], ab[LN_MAXV * VEC];
@@ -102,7 +104,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) {
                     const float xh = (xr[i + q] - mu) * rs;
-                    dr[i + q] = rs * (gr[i + q] * gamma[i + q] - s1 - xh * s2);
+                    const float v = rs * (gr[i + q] * gamma[i + q] - s1 - xh * s2);
+                    dr[i + q] = v;
+                    if (MASK) dxm[(size_t)row * dim + i + q] = v * mask[(size_t)row * dim + i + q];
                 }
             }
         }
@@ -122,6 +126,19 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
     for (int e = threadIdx.x; e < 2 * dim; e += 256) {
         const float a = red[e] + red[2 * dim + e] + red[4 * dim + e] + red[6 * dim + e];
         partial[(size_t)blockIdx.x * 2 * dim + e] = a;
+    }
+}
+
+// y = x * mask, 4 floats per thread: a Dropout keep-mask applied to a gradient that no library epilogue produces (the
+// incoming gradient of ops.TransformerLayer, networks.py:133)
+__global__ __launch_bounds__(256) void mask_mul_kernel(const float* __restrict__ x, const float* __restrict__ mask,
+                                                       float* __restrict__ y, long n) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(x + i), m = *reinterpret_cast<const f32x4*>(mask + i);
+        *reinterpret_cast<f32x4*>(y + i) = f32x4{a[0] * m[0], a[1] * m[1], a[2] * m[2], a[3] * m[3]};
+    } else {
+        for (long j = i; j < n; ++j) y[j] = x[j] * mask[j];
     }
 }
 
@@ -363,6 +380,30 @@ extern "C" int tmf_layernorm_bwd(const float* x, const float* gamma, const float
     if (vec == 4) hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb);
     else          hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb);
     return tmf_launch_result("tmf_layernorm_bwd");
+}
+
+extern "C" int tmf_layernorm_bwd_masked(const float* x, const float* gamma, const float* mean, const float* rstd,
+                                        const float* dy, float* dx, float* partial, int rows, int dim,
+                                        const float* mask, float* dx_masked, void* stream) {
+    TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(gamma); TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(rstd);
+    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(partial); TMF_REQUIRE_PTR(mask); TMF_REQUIRE_PTR(dx_masked);
+    TMF_REQUIRE(rows > 0 && dim > 0, TMF_E_SHAPE, "tmf_layernorm_bwd_masked: rows=%d dim=%d", rows, dim);
+    const int vec = dim % 4 == 0 ? 4 : 1;
+    TMF_REQUIRE(dim <= 64 * vec * LN_MAXV, TMF_E_SHAPE, "tmf_layernorm_bwd_masked: dim=%d exceeds %d", dim, 64 * vec * LN_MAXV);
+    const int rpb = ln_rows_per_block(rows);
+    dim3 grid(tmf_cdiv(rows, rpb)), block(256);
+    const size_t lds = (size_t)8 * dim * 4;
+    if (vec == 4) hipLaunchKernelGGL((layernorm_bwd_kernel<4, true>), grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb, mask, dx_masked);
+    else          hipLaunchKernelGGL((layernorm_bwd_kernel<1, true>), grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb, mask, dx_masked);
+    return tmf_launch_result("tmf_layernorm_bwd_masked");
+}
+
+extern "C" int tmf_mask_mul(const float* x, const float* mask, float* y, long n, void* stream) {
+    TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(mask); TMF_REQUIRE_PTR(y);
+    TMF_REQUIRE_ALIGNED(x); TMF_REQUIRE_ALIGNED(mask); TMF_REQUIRE_ALIGNED(y);
+    TMF_REQUIRE(n > 0 && n < (1L << 40), TMF_E_SHAPE, "tmf_mask_mul: n=%ld", n);
+    hipLaunchKernelGGL(mask_mul_kernel, dim3((unsigned)tmf_cdiv(n, 1024L)), dim3(256), 0, (hipStream_t)stream, x, mask, y, n);
+    return tmf_launch_result("tmf_mask_mul");
 }
 
 extern "C" int tmf_token_pool_fwd(const float* mri, const float* pet, float* cls, int32_t* argmax,

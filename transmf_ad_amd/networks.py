@@ -224,12 +224,28 @@ class Transformer(nn.Module):
             self._drops = [m for m in self.modules() if isinstance(m, nn.Dropout) or hasattr(m, "tmf_keep_mask")]
         return any(m.training and (hasattr(m, "tmf_keep_mask") or m.p > 0) for m in self._drops)
 
-    def _fused(self, x, allow_dropout=False):
+    def _dropout_hooked(self):
+        """A Dropout module with forward hooks of its own: they must fire, so this Transformer keeps the module path."""
+        self._dropout_active()
+        return any(m._forward_hooks or m._forward_pre_hooks for m in self._drops)
+
+    def _fused(self, x, allow_dropout=True):
+        """The token-GEMM path (ops.TransformerLayer) takes this forward.  Active Dropout rides along as keep-masks in the
+        Linears' epilogues (every dim the token GEMMs take) unless a Dropout module is hooked or the caller says no."""
         attn, ff = self.layers[0]
         a, f = attn.fn, ff.fn
-        drop = (not allow_dropout) and self._dropout_active()
+        drop = self._dropout_active() and (not allow_dropout or self._dropout_hooked())
         return (not drop) and x.is_cuda and ops.fused_block_supported(x.shape[-1], a.to_q.out_features,
                                                                       f.net[0].out_features)
+
+    def _keep_masks(self, x):
+        """Every keep-mask of this forward in one launch (ops.dropout_keep_masks): per layer (to_out, GELU, 2nd Linear)."""
+        R, dim = x.shape[0] * x.shape[1], x.shape[-1]
+        req = []
+        for attn, ff in self.layers:
+            req += [(attn.fn.to_out[1], (R, dim)), (ff.fn.net[2], (R, ff.fn.net[0].out_features)), (ff.fn.net[4], (R, dim))]
+        mk = ops.dropout_keep_masks(req, x.device)
+        return [tuple(mk[3 * i:3 * i + 3]) for i in range(len(self.layers))]
 
     @device_guard
     def forward(self, x, context=None, residual=None):
@@ -240,8 +256,9 @@ class Transformer(nn.Module):
         # CURRENT layer (networks.py:162 `default(context, x)` sees the normalised x), which the op-per-launch
         # branch below reproduces.
         if context is not None and self._fused(x):
-            for attn, ff in self.layers:
-                x = ops.transformer_layer(x, context, attn.norm, attn.fn, ff.norm, ff.fn)
+            masks = self._keep_masks(x) if self._dropout_active() else [None] * len(self.layers)
+            for (attn, ff), mk in zip(self.layers, masks):
+                x = ops.transformer_layer(x, context, attn.norm, attn.fn, ff.norm, ff.fn, mk)
         else:
             for attn, ff in self.layers:
                 x = attn(x, context=context) + x
@@ -276,8 +293,8 @@ class CrossTransformer_MOD_AVG(nn.Module):
         self.gmp = _TokenReduce("max")
 
     def _one_call_ok(self, mri_tokens):
-        """dim 64, 128 or 256, depth-1 Transformer instances, dropout inactive, nobody listening on the inner modules:
-        the whole fusion is one library call per pass (ops.FusionTrain)."""
+        """dim 64, 128 or 256, depth-1 Transformer instances, nobody listening on the inner modules (Dropout's included):
+        the whole fusion is one library call per pass (ops.FusionTrain), active Dropout as keep-masks."""
         if not (mri_tokens.is_cuda and torch.is_grad_enabled()) or len(self.layers) == 0:
             return False
         t0 = self.layers[0][0]
@@ -286,9 +303,9 @@ class CrossTransformer_MOD_AVG(nn.Module):
         if not ops.fusion_one_call_supported(mri_tokens.shape[-1], inner, f.net[0].out_features, inner // a.heads,
                                              len(self.layers)):
             return False
-        # Dropout (options/option.py:39) stays on the HIP path where the fused per-instance kernels take the masks
-        masks_ok = ops.fusion_fused_supported(mri_tokens.shape[1], mri_tokens.shape[-1], a.heads, inner // a.heads,
-                                              f.net[0].out_features)
+        # Dropout (options/option.py:39): the one-call entry takes keep-masks for every geometry it accepts (the fused
+        # per-instance kernels at dim 128, one launch per op elsewhere)
+        masks_ok = ops.fusion_takes_masks(mri_tokens.shape[-1], inner, f.net[0].out_features, inner // a.heads)
         for pair in self.layers:
             for tr in pair:
                 if (len(tr.layers) != 1 or not tr._fused(mri_tokens, allow_dropout=masks_ok) or tr._forward_hooks

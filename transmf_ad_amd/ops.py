@@ -868,9 +868,11 @@ def layer_norm(x, gamma, beta, eps=1e-5, residual=None):
 # residual around it (csrc/token_gemm.hip).                         (networks.py:114-175, 215-230)
 # --------------------------------------------------------------------------------------
 
-def tok_linear_fwd(x, w, bias=None, residual=None, ln=None, gelu=False, keep_ln_out=False):
+def tok_linear_fwd(x, w, bias=None, residual=None, ln=None, gelu=False, keep_ln_out=False, mask=None):
     """y = [GELU](LayerNorm?(x) @ w.T + bias) + residual on 2-D row-major fp32 tensors.
-    ln = (gamma, beta, eps).  Returns (y, ln_saved, pre): ln_saved = (mean, rstd, normalised rows | None)."""
+    ln = (gamma, beta, eps).  mask: a scaled Dropout keep-mask (R, Nout) applied before the residual / after the GELU
+    (tmf_tok_linear_fwd_masked; `pre` stays unmasked).  Returns (y, ln_saved, pre): ln_saved = (mean, rstd, normalised
+    rows | None)."""
     R, K = x.shape
     nout = w.shape[0]
     y = torch.empty((R, nout), device=x.device, dtype=_f32)
@@ -885,15 +887,21 @@ def tok_linear_fwd(x, w, bias=None, residual=None, ln=None, gelu=False, keep_ln_
             ln_out = torch.empty((R, K), device=x.device, dtype=_f32)
     if gelu:
         pre = torch.empty((R, nout), device=x.device, dtype=_f32)
-    _lib.call("tmf_tok_linear_fwd", x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), R, K, nout,
-              _ptr(g), _ptr(b), float(eps), _ptr(mean), _ptr(rstd), _ptr(ln_out), _ptr(pre), _stream())
+    args = (x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), R, K, nout, _ptr(g), _ptr(b), float(eps),
+            _ptr(mean), _ptr(rstd), _ptr(ln_out), _ptr(pre))
+    if mask is None:
+        _lib.call("tmf_tok_linear_fwd", *args, _stream())
+    else:
+        _lib.call("tmf_tok_linear_fwd_masked", *args, _chk(mask, "mask").data_ptr(), _stream())
     return y, (mean, rstd, ln_out), pre
 
 
 def tok_linear_bwd_input(dy, w, gelu_pre=None, ln=None, add1=None, add2=None, ln_partial=None, bias_partial=None,
-                         partial_stride=0):
+                         partial_stride=0, mask=None, mask_out=None):
     """dx = E(dy @ w); ln = (x, mean, rstd, gamma) selects the LayerNorm-backward epilogue.  ln_partial /
-    bias_partial are (tensor, column offset) pairs into one [row blocks][partial_stride] workspace."""
+    bias_partial are (tensor, column offset) pairs into one [row blocks][partial_stride] workspace.  mask: a scaled
+    Dropout keep-mask (R, K) (tmf_tok_linear_bwd_input_masked): with gelu_pre it multiplies the GELU gradient, with ln
+    the epilogue also writes mask * dx to `mask_out`."""
     R, nout = dy.shape
     K = w.shape[1]
     dx = torch.empty((R, K), device=dy.device, dtype=_f32)
@@ -903,10 +911,23 @@ def tok_linear_bwd_input(dy, w, gelu_pre=None, ln=None, add1=None, add2=None, ln
 
     def off(pair):
         return None if pair is None else pair[0].data_ptr() + 4 * pair[1]
-    _lib.call("tmf_tok_linear_bwd_input", dy.data_ptr(), w.data_ptr(), dx.data_ptr(), R, nout, K, _ptr(gelu_pre),
-              _ptr(lx), _ptr(lm), _ptr(lr), _ptr(lg), _ptr(add1), _ptr(add2), off(ln_partial), off(bias_partial),
-              partial_stride, _stream())
+    args = (dy.data_ptr(), w.data_ptr(), dx.data_ptr(), R, nout, K, _ptr(gelu_pre), _ptr(lx), _ptr(lm), _ptr(lr), _ptr(lg),
+            _ptr(add1), _ptr(add2), off(ln_partial), off(bias_partial), partial_stride)
+    if mask is None:
+        _lib.call("tmf_tok_linear_bwd_input", *args, _stream())
+    else:
+        _lib.call("tmf_tok_linear_bwd_input_masked", *args, _chk(mask, "mask").data_ptr(), _ptr(mask_out), _stream())
     return dx
+
+
+def mask_mul(x, mask):
+    """x * mask (a scaled Dropout keep-mask of x's shape) in one launch (tmf_mask_mul)."""
+    x, mask = _chk(x, "x"), _chk(mask, "mask")
+    if mask.shape != x.shape:
+        raise _lib.TmfError(f"mask_mul: mask {tuple(mask.shape)} vs x {tuple(x.shape)}")
+    y = torch.empty_like(x)
+    _lib.call("tmf_mask_mul", x.data_ptr(), mask.data_ptr(), y.data_ptr(), x.numel(), _stream())
+    return y
 
 
 # False / TMF_FUSE_TOKENS=0: every op of the block is its own launch (kept for A/B measurements and tests)
@@ -947,10 +968,13 @@ def fused_block_supported(dim, inner, mlp):
 class TransformerLayer(torch.autograd.Function):
     """x <- Attention(LayerNorm(x), context) + x ; x <- FeedForward(LayerNorm(x)) + x   as 6 launches forward
     (to_q with LayerNorm prologue, to_kv, attention, to_out + bias + x, Linear + bias + GELU with LayerNorm
-    prologue, Linear + bias + x) and 7 + 1 (all five weight gradients) + 2 reductions backward."""
+    prologue, Linear + bias + x) and 7 + 1 (all five weight gradients) + 2 reductions backward.  masks = the scaled
+    Dropout keep-masks (m_o (R, dim), m_g (R, mlp), m_f (R, dim); any may be None) of networks.py:153, :131, :133, applied
+    in the Linears' epilogues; backward multiplies its incoming gradient by m_f in one extra launch (tmf_mask_mul)."""
 
     @staticmethod
-    def forward(ctx, x, context, g1, b1n, wq, wkv, wo, bo, g2, b2n, w1, b1, w2, b2, heads, scale, eps1, eps2):
+    def forward(ctx, x, context, g1, b1n, wq, wkv, wo, bo, g2, b2n, w1, b1, w2, b2, heads, scale, eps1, eps2, masks=None):
+        mo, mg, mf = masks if masks is not None else (None, None, None)
         x, context = _chk(x, "x"), _chk(context, "context")
         B, N, dim = x.shape
         M = context.shape[1]
@@ -963,12 +987,13 @@ class TransformerLayer(torch.autograd.Function):
         lse = torch.empty((B, heads, N), device=x.device, dtype=_f32)
         _lib.call("tmf_xattn_fwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, out.data_ptr(),
                   lse.data_ptr(), B, heads, N, M, dh, inner, 2 * inner, float(scale), _stream())
-        x1, _, _ = tok_linear_fwd(out, wo, bias=bo, residual=x2d)
-        g, (mean2, rstd2, f), h = tok_linear_fwd(x1, w1, bias=b1, ln=(g2, b2n, eps2), gelu=True, keep_ln_out=True)
-        x2, _, _ = tok_linear_fwd(g, w2, bias=b2, residual=x1)
+        x1, _, _ = tok_linear_fwd(out, wo, bias=bo, residual=x2d, mask=mo)
+        g, (mean2, rstd2, f), h = tok_linear_fwd(x1, w1, bias=b1, ln=(g2, b2n, eps2), gelu=True, keep_ln_out=True, mask=mg)
+        x2, _, _ = tok_linear_fwd(g, w2, bias=b2, residual=x1, mask=mf)
         ctx.save_for_backward(x2d, c2d, g1, wq, wkv, wo, g2, w1, w2, mean1, rstd1, a, q, kv, out, lse, x1, mean2,
                               rstd2, f, h, g)
         ctx.cfg = (B, N, M, dim, inner, heads, float(scale))
+        ctx.masks = (mo, mg, mf)
         return x2.view(B, N, dim)
 
     @staticmethod
@@ -984,10 +1009,17 @@ class TransformerLayer(torch.autograd.Function):
         o_b2, o_b1, o_bo, o_ln2, o_ln1 = 0, dim, dim + mlp, 2 * dim + mlp, 4 * dim + mlp
         stride = 6 * dim + mlp
         part = torch.empty((nblk, stride), device=dx2.device, dtype=_f32)
-        dh_ = tok_linear_bwd_input(dx2, w2, gelu_pre=h, bias_partial=(part, o_b2), partial_stride=stride)
+        # Dropout: e_f = m_f dx2 and e_o = m_o dx1 are the dy of the second FeedForward Linear and of to_out; the residual
+        # paths carry the unmasked dx2 / dx1
+        mo, mg, mf = ctx.masks
+        ef = dx2 if mf is None else mask_mul(dx2, mf)
+        dh_ = tok_linear_bwd_input(ef, w2, gelu_pre=h, bias_partial=(part, o_b2), partial_stride=stride, mask=mg)
+        eo = None if mo is None else torch.empty((R, dim), device=dx2.device, dtype=_f32)
         dx1 = tok_linear_bwd_input(dh_, w1, ln=(x1, mean2, rstd2, g2), add1=dx2, ln_partial=(part, o_ln2),
-                                   bias_partial=(part, o_b1), partial_stride=stride)
-        dout = tok_linear_bwd_input(dx1, wo, bias_partial=(part, o_bo), partial_stride=stride)
+                                   bias_partial=(part, o_b1), partial_stride=stride, mask=mo, mask_out=eo)
+        if eo is None:
+            eo = dx1
+        dout = tok_linear_bwd_input(eo, wo, bias_partial=(part, o_bo), partial_stride=stride)
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         dhd = inner // heads
@@ -999,19 +1031,22 @@ class TransformerLayer(torch.autograd.Function):
                                   partial_stride=stride)
         sums = torch.empty(stride, device=dx2.device, dtype=_f32)
         _lib.call("tmf_colsum_finalize", part.data_ptr(), nblk, stride, sums.data_ptr(), _stream())
-        dw2, dw1, dwo, dwkv, dwq = tok_wgrad_multi([(dx2, g), (dh_, f), (dx1, out), (dkv, c2d), (dq, a)])
+        dw2, dw1, dwo, dwkv, dwq = tok_wgrad_multi([(ef, g), (dh_, f), (eo, out), (dkv, c2d), (dq, a)])
         return (dx.view(B, N, dim), None if dctx is None else dctx.view(B, M, dim),
                 sums[o_ln1:o_ln1 + dim], sums[o_ln1 + dim:o_ln1 + 2 * dim], dwq, dwkv, dwo, sums[o_bo:o_bo + dim],
                 sums[o_ln2:o_ln2 + dim], sums[o_ln2 + dim:o_ln2 + 2 * dim], dw1, sums[o_b1:o_b1 + mlp], dw2,
-                sums[o_b2:o_b2 + dim], None, None, None, None)
+                sums[o_b2:o_b2 + dim], None, None, None, None, None)
 
 
-def transformer_layer(x, context, ln1, attn, ln2, ff):
-    """ln1 / ln2: nn.LayerNorm; attn: networks.Attention; ff: networks.FeedForward (parameter containers)."""
+def transformer_layer(x, context, ln1, attn, ln2, ff, masks=None):
+    """ln1 / ln2: nn.LayerNorm; attn: networks.Attention; ff: networks.FeedForward (parameter containers); masks: the
+    layer's scaled Dropout keep-masks (to_out, after GELU, after the second Linear) or None."""
+    if masks is not None and all(m is None for m in masks):
+        masks = None
     return TransformerLayer.apply(x, context, ln1.weight, ln1.bias, attn.to_q.weight, attn.to_kv.weight,
                                   attn.to_out[0].weight, attn.to_out[0].bias, ln2.weight, ln2.bias,
                                   ff.net[0].weight, ff.net[0].bias, ff.net[3].weight, ff.net[3].bias,
-                                  attn.heads, attn.scale, ln1.eps, ln2.eps)
+                                  attn.heads, attn.scale, ln1.eps, ln2.eps, masks)
 
 
 # --------------------------------------------------------------------------------------
@@ -1094,6 +1129,12 @@ def dropout_keep_masks(requests, device):
 def fusion_one_call_supported(dim, inner, mlp, dim_head, depth):
     return (FUSION_ONE_CALL and FUSE_TOKEN_LINEARS and dim in TOKEN_GEMM_DIMS and inner % 64 == 0 and mlp % 64 == 0
             and dim_head in (8, 16, 32, 64) and 0 < depth <= 16)
+
+
+def fusion_takes_masks(dim, inner, mlp, dim_head):
+    """Geometries whose one-call fusion entry takes Dropout keep-masks (tmf_fusion_takes_masks): every one it accepts —
+    the fused per-instance kernels at dim 128 apply them, one launch per op (token_gemm.hip's masked epilogues) elsewhere."""
+    return dim in TOKEN_GEMM_DIMS and inner % 64 == 0 and mlp % 64 == 0 and dim_head in (8, 16, 32, 64)
 
 
 class FusionTrain(torch.autograd.Function):
