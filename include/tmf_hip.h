@@ -346,6 +346,17 @@ int tmf_xattn_bwd(const float* q, const float* k, const float* v, const float* o
                   const float* dout, float* dq, float* dk, float* dv,
                   int B, int heads, int N, int M, int dh, int q_stride, int kv_stride, int dkv_stride,
                   float scale, void* stream);
+/* Two-part context (CrossTransformer, networks.py:250-251: keys / values over torch.cat([mri, pet], 1)): context row j
+ * of batch b is row j of k1 / v1 ([B][M1][*]) when j < M1, else row j - M1 of k2 / v2 ([B][M2][*]); no concatenated copy
+ * is built.  dk1 / dv1 and dk2 / dv2 receive the two parts' gradients in the same layouts (rows of stride dkv_stride).
+ * Otherwise as tmf_xattn_fwd / _bwd with M = M1 + M2; M1, M2 > 0. */
+int tmf_xattn_fwd_cat(const float* q, const float* k1, const float* v1, const float* k2, const float* v2, float* out,
+                      float* lse, int B, int heads, int N, int M1, int M2, int dh, int q_stride, int kv_stride, float scale,
+                      void* stream);
+int tmf_xattn_bwd_cat(const float* q, const float* k1, const float* v1, const float* k2, const float* v2, const float* out,
+                      const float* lse, const float* dout, float* dq, float* dk1, float* dv1, float* dk2, float* dv2,
+                      int B, int heads, int N, int M1, int M2, int dh, int q_stride, int kv_stride, int dkv_stride,
+                      float scale, void* stream);
 
 /* ------------------------------------------------------------------------------
  * LayerNorm over the last dim (networks.py:117,219) and the token pooling of

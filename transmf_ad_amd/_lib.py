@@ -97,6 +97,8 @@ PROTOTYPES = {
     "tmf_colsum_finalize": (_i, [_p, _i, _i, _p, _p]),
     "tmf_xattn_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "tmf_xattn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "tmf_xattn_fwd_cat": (_i, [_p] * 7 + [_i] * 8 + [_f, _p]),
+    "tmf_xattn_bwd_cat": (_i, [_p] * 13 + [_i] * 9 + [_f, _p]),
     "tmf_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     "tmf_pack_conv_weights": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "tmf_pack_conv_weights_bf16": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -17,6 +17,10 @@
 // SIMDs (the two splits of a tile are adjacent waves, i.e. different SIMDs of the CU).  The two partial results of a tile
 // are merged through LDS (online-softmax merge in the forward, plain sums in the backward), in a fixed order.
 //
+// Two-part contexts (tmf_xattn_fwd_cat / _bwd_cat): CrossTransformer (networks.py:250-251) attends over
+// torch.cat([mri, pet], 1).  The kernels read key / value row j of batch b from the first part when j < M1, else row
+// j - M1 of the second part, and write dK / dV back the same way, so the concatenated context is never built.
+//
 // Replaces, at /root/reference/models/networks.py:166-174: the three rearranges, einsum
 // 'bhid,bhjd->bhij' * scale, Softmax(dim=-1), einsum 'bhij,bhjd->bhid' and their backward.
 #include "tmf_common.h"
@@ -49,11 +53,13 @@ __device__ __forceinline__ void mma_cols(f32x16& acc, const float* lds, int row0
 }
 
 // Stage `nrows` rows (zero-filled past `limit`) of a [*, stride] matrix, columns [col0, col0+DH), into lds[(DH+1)].
+// Rows g < split are row g of `src`, rows g >= split row g - split of `src2` (a two-part context read in place;
+// split >= limit: one matrix).
 // 16-byte global loads, eight in flight per thread before the first LDS write (the whole K/V panel of a head is
 // two or three such batches: the staging is bandwidth- not latency-bound).  Needs stride % 4 == 0, col0 % 4 == 0.
 template <int DH>
-__device__ __forceinline__ void stage_rows(float* lds, const float* src, int stride, int col0, int first, int nrows,
-                                           int limit, int tid, int nthreads) {
+__device__ __forceinline__ void stage_rows(float* lds, const float* src, const float* src2, int split, int stride, int col0,
+                                           int first, int nrows, int limit, int tid, int nthreads) {
     constexpr int Q = DH / 4;                 // float4 per row
     constexpr int BATCH = 8;
     const int total = nrows * Q;
@@ -65,7 +71,10 @@ __device__ __forceinline__ void stage_rows(float* lds, const float* src, int str
             const int r = e / Q, c = (e % Q) * 4;
             const int g = first + r;
             f32x4 t = {0.f, 0.f, 0.f, 0.f};
-            if (e < total && g < limit) t = *reinterpret_cast<const f32x4*>(src + (size_t)g * stride + col0 + c);
+            if (e < total && g < limit) {
+                const float* row = g < split ? src + (size_t)g * stride : src2 + (size_t)(g - split) * stride;
+                t = *reinterpret_cast<const f32x4*>(row + col0 + c);
+            }
             v[u] = t;
         }
 #pragma unroll
@@ -79,10 +88,11 @@ __device__ __forceinline__ void stage_rows(float* lds, const float* src, int str
     }
 }
 
+// k, v: the first M1 context rows of every batch ([B][M1][*]); k2, v2: the other M - M1 ([B][M - M1][*]; unused when M1 == M)
 template <int DH>
 __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_fwd_kernel(   // <= 256 registers: MFMA results stay in VGPRs
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-    float* __restrict__ out, float* __restrict__ lse, int heads, int N, int M, int q_stride, int kv_stride,
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const float* k2, const float* v2,
+    float* __restrict__ out, float* __restrict__ lse, int heads, int N, int M, int M1, int q_stride, int kv_stride,
     float scale, int sb) {
     constexpr int DT = (DH + 31) / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -94,8 +104,10 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_fwd_kernel(   // 
     const int ksp = wave & 1;                                // which half of the key chunks this wave takes
     const int q0 = (blockIdx.x * 2 + (wave >> 1)) * 32;
     const float* qb = q + (size_t)b * N * q_stride;
-    const float* kb = k + (size_t)b * M * kv_stride;
-    const float* vb = v + (size_t)b * M * kv_stride;
+    const float* kb = k + (size_t)b * M1 * kv_stride;
+    const float* vb = v + (size_t)b * M1 * kv_stride;
+    const float* kb2 = k2 + (size_t)b * (M - M1) * kv_stride;
+    const float* vb2 = v2 + (size_t)b * (M - M1) * kv_stride;
 
     float qreg[DH / 2];
     {
@@ -116,8 +128,8 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_fwd_kernel(   // 
         const int nrows = (M - sb0) < sb ? (M - sb0) : sb;
         const int nrows_pad = (nrows + 31) & ~31;
         if (sb0 > 0) __syncthreads();
-        stage_rows<DH>(Ks, kb, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
-        stage_rows<DH>(Vs, vb, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
+        stage_rows<DH>(Ks, kb, kb2, M1, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
+        stage_rows<DH>(Vs, vb, vb2, M1, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
         __syncthreads();
         if (q0 < N) {
             for (int kt0 = 0; kt0 < nrows_pad / 32; kt0 += KC) {
@@ -215,9 +227,9 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_fwd_kernel(   // 
 // dQ: same geometry as the forward (K, V resident in LDS; a wave owns 32 queries).
 template <int DH>
 __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dq_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const float* k2, const float* v2,
     const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout,
-    float* __restrict__ dq, int heads, int N, int M, int q_stride, int kv_stride, float scale, int sb) {
+    float* __restrict__ dq, int heads, int N, int M, int M1, int q_stride, int kv_stride, float scale, int sb) {
     constexpr int DT = (DH + 31) / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
@@ -229,8 +241,10 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dq_kernel(
     const int q0 = (blockIdx.x * 2 + (wave >> 1)) * 32;
     const int qi = q0 + l31;
     const float* qb = q + (size_t)b * N * q_stride;
-    const float* kb = k + (size_t)b * M * kv_stride;
-    const float* vb = v + (size_t)b * M * kv_stride;
+    const float* kb = k + (size_t)b * M1 * kv_stride;
+    const float* vb = v + (size_t)b * M1 * kv_stride;
+    const float* kb2 = k2 + (size_t)b * (M - M1) * kv_stride;
+    const float* vb2 = v2 + (size_t)b * (M - M1) * kv_stride;
     const int inner = heads * DH;
 
     float qreg[DH / 2], doreg[DH / 2];
@@ -258,8 +272,8 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dq_kernel(
         const int nrows = (M - sb0) < sb ? (M - sb0) : sb;
         const int nrows_pad = (nrows + 31) & ~31;
         if (sb0 > 0) __syncthreads();
-        stage_rows<DH>(Ks, kb, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
-        stage_rows<DH>(Vs, vb, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
+        stage_rows<DH>(Ks, kb, kb2, M1, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
+        stage_rows<DH>(Vs, vb, vb2, M1, kv_stride, h * DH, sb0, nrows_pad, M, tid, 256);
         __syncthreads();
         if (q0 < N) {
             for (int kt = ksp; kt < nrows_pad / 32; kt += 2) {
@@ -311,12 +325,13 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dq_kernel(
     }
 }
 
-// dK, dV: a wave owns 32 keys; Q and dO (all queries) are resident in LDS with lse / delta.
+// dK, dV: a wave owns 32 keys; Q and dO (all queries) are resident in LDS with lse / delta.  Key rows j >= M1 are row
+// j - M1 of the second context part: read from k2 / v2, their gradients written to dk2 / dv2.
 template <int DH>
 __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    const float* __restrict__ q, const float* k, const float* v, const float* k2, const float* v2,
     const float* __restrict__ out, const float* __restrict__ lse, const float* __restrict__ dout,
-    float* __restrict__ dk, float* __restrict__ dv, int heads, int N, int M, int q_stride, int kv_stride,
+    float* dk, float* dv, float* dk2, float* dv2, int heads, int N, int M, int M1, int q_stride, int kv_stride,
     int dkv_stride, float scale, int sb) {
     constexpr int DT = (DH + 31) / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -331,8 +346,10 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
     const int k0 = (blockIdx.x * 2 + (wave >> 1)) * 32;
     const int ki = k0 + l31;
     const float* qb = q + (size_t)b * N * q_stride;
-    const float* kb = k + (size_t)b * M * kv_stride;
-    const float* vb = v + (size_t)b * M * kv_stride;
+    const bool part1 = ki < M1;                              // this lane's key row lies in the first context part
+    const size_t krow = part1 ? (size_t)b * M1 + ki : (size_t)b * (M - M1) + (ki - M1);
+    const float* kr = (part1 ? k : k2) + krow * kv_stride;
+    const float* vr = (part1 ? v : v2) + krow * kv_stride;
     const int inner = heads * DH;
     const float* dob = dout + (size_t)b * N * inner;
     const float* ob = out + (size_t)b * N * inner;
@@ -342,8 +359,8 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
 #pragma unroll
     for (int s = 0; s < DH / 2; ++s) {
         const int d = h * DH + 2 * s + hsel;
-        kreg[s] = ki < M ? kb[(size_t)ki * kv_stride + d] : 0.f;
-        vreg[s] = ki < M ? vb[(size_t)ki * kv_stride + d] : 0.f;
+        kreg[s] = ki < M ? kr[d] : 0.f;
+        vreg[s] = ki < M ? vr[d] : 0.f;
     }
     f32x16 dkT[DT], dvT[DT];
 #pragma unroll
@@ -355,8 +372,8 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
         const int nrows = (N - sb0) < sb ? (N - sb0) : sb;
         const int nrows_pad = (nrows + 31) & ~31;
         if (sb0 > 0) __syncthreads();
-        stage_rows<DH>(Qs, qb, q_stride, h * DH, sb0, nrows_pad, N, tid, 256);
-        stage_rows<DH>(Ds, dob, inner, h * DH, sb0, nrows_pad, N, tid, 256);
+        stage_rows<DH>(Qs, qb, qb, N, q_stride, h * DH, sb0, nrows_pad, N, tid, 256);
+        stage_rows<DH>(Ds, dob, dob, N, inner, h * DH, sb0, nrows_pad, N, tid, 256);
         for (int r = tid; r < nrows_pad; r += 256) {
             const int g = sb0 + r;
             float dl = 0.f, ls = 0.f;
@@ -414,8 +431,8 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
             for (int r = 0; r < 16; ++r) { dkT[dt][r] += xch[dt * 32 + r]; dvT[dt][r] += xch[dt * 32 + 16 + r]; }
     }
     if (ki < M) {
-        float* dkb = dk + ((size_t)b * M + ki) * dkv_stride + h * DH;
-        float* dvb = dv + ((size_t)b * M + ki) * dkv_stride + h * DH;
+        float* dkb = (part1 ? dk : dk2) + krow * dkv_stride + h * DH;
+        float* dvb = (part1 ? dv : dv2) + krow * dkv_stride + h * DH;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -456,7 +473,11 @@ int check_attn(const char* fn, int B, int heads, int N, int M, int dh, int q_str
     return TMF_OK;
 }
 
-}  // namespace
+// the two context parts of a _cat entry: both non-empty, M1 + M2 an int
+int check_parts(const char* fn, int M1, int M2) {
+    TMF_REQUIRE(M1 > 0 && M2 > 0 && M1 <= 0x7fffffff - M2, TMF_E_SHAPE, "%s: context parts of %d and %d rows", fn, M1, M2);
+    return TMF_OK;
+}
 
 #define TMF_DH_SWITCH(dh, CALL)            \
     switch (dh) {                          \
@@ -466,6 +487,51 @@ int check_attn(const char* fn, int B, int heads, int N, int M, int dh, int q_str
         default: { CALL(64); break; }      \
     }
 
+// The launches behind the public entries (which check pointers and shapes): context rows [0, M1) of every batch from
+// k / v, rows [M1, M) from k2 / v2.
+int xattn_fwd_launch(const char* fn, const float* q, const float* k, const float* v, const float* k2, const float* v2,
+                     float* out, float* lse, int B, int heads, int N, int M, int M1, int dh, int q_stride, int kv_stride,
+                     float scale, void* stream) {
+    TMF_REQUIRE((heads * dh) % 4 == 0, TMF_E_SHAPE, "%s: heads*dh must be a multiple of 4", fn);
+    const int sb = resident_rows(M, dh);
+    const size_t lds = lds_two(sb, dh);
+    dim3 grid(tmf_cdiv(N, 64), heads, B), block(256);
+    int rc = TMF_OK;
+#define CALL(DH)                                                                                     \
+    auto kf = xattn_fwd_kernel<DH>;                                                                  \
+    if ((rc = tmf_allow_lds(kf, lds, fn))) return rc;                                                \
+    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)stream, q, k, v, k2, v2, out, lse, heads, N, M, M1, \
+                       q_stride, kv_stride, scale, sb);
+    TMF_DH_SWITCH(dh, CALL)
+#undef CALL
+    return tmf_launch_result(fn);
+}
+
+int xattn_bwd_launch(const char* fn, const float* q, const float* k, const float* v, const float* k2, const float* v2,
+                     const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv, float* dk2,
+                     float* dv2, int B, int heads, int N, int M, int M1, int dh, int q_stride, int kv_stride, int dkv_stride,
+                     float scale, void* stream) {
+    const int sbk = resident_rows(M, dh), sbq = resident_rows(N, dh);
+    const size_t lds_q = lds_two(sbk, dh), lds_kv = lds_dkv(sbq, dh);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = TMF_OK;
+#define CALL(DH)                                                                                          \
+    auto kq = xattn_bwd_dq_kernel<DH>;                                                                    \
+    auto kk = xattn_bwd_dkv_kernel<DH>;                                                                   \
+    if ((rc = tmf_allow_lds(kq, lds_q, fn))) return rc;                                                   \
+    if ((rc = tmf_allow_lds(kk, lds_kv, fn))) return rc;                                                  \
+    hipLaunchKernelGGL(kq, dim3(tmf_cdiv(N, 64), heads, B), dim3(256), lds_q, s, q, k, v, k2, v2, out, lse, dout, dq, \
+                       heads, N, M, M1, q_stride, kv_stride, scale, sbk);                                 \
+    if ((rc = tmf_launch_result("tmf_xattn_bwd(dq)"))) return rc;                                         \
+    hipLaunchKernelGGL(kk, dim3(tmf_cdiv(M, 64), heads, B), dim3(256), lds_kv, s, q, k, v, k2, v2, out, lse, dout, dk, dv, \
+                       dk2, dv2, heads, N, M, M1, q_stride, kv_stride, dkv_stride, scale, sbq);
+    TMF_DH_SWITCH(dh, CALL)
+#undef CALL
+    return tmf_launch_result("tmf_xattn_bwd(dkv)");
+}
+
+}  // namespace
+
 extern "C" int tmf_xattn_fwd(const float* q, const float* k, const float* v, float* out, float* lse,
                              int B, int heads, int N, int M, int dh, int q_stride, int kv_stride, float scale,
                              void* stream) {
@@ -473,18 +539,22 @@ extern "C" int tmf_xattn_fwd(const float* q, const float* k, const float* v, flo
     int rc = check_attn("tmf_xattn_fwd", B, heads, N, M, dh, q_stride, kv_stride);
     if (rc) return rc;
     TMF_REQUIRE_ALIGNED(out); TMF_REQUIRE_ALIGNED(q); TMF_REQUIRE_ALIGNED(k); TMF_REQUIRE_ALIGNED(v);
-    TMF_REQUIRE((heads * dh) % 4 == 0, TMF_E_SHAPE, "tmf_xattn_fwd: heads*dh must be a multiple of 4");
-    const int sb = resident_rows(M, dh);
-    const size_t lds = lds_two(sb, dh);
-    dim3 grid(tmf_cdiv(N, 64), heads, B), block(256);
-#define CALL(DH)                                                                                     \
-    auto kf = xattn_fwd_kernel<DH>;                                                                  \
-    if ((rc = tmf_allow_lds(kf, lds, "tmf_xattn_fwd"))) return rc;                                   \
-    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)stream, q, k, v, out, lse, heads, N, M,    \
-                       q_stride, kv_stride, scale, sb);
-    TMF_DH_SWITCH(dh, CALL)
-#undef CALL
-    return tmf_launch_result("tmf_xattn_fwd");
+    return xattn_fwd_launch("tmf_xattn_fwd", q, k, v, k, v, out, lse, B, heads, N, M, M, dh, q_stride, kv_stride, scale,
+                            stream);
+}
+
+extern "C" int tmf_xattn_fwd_cat(const float* q, const float* k1, const float* v1, const float* k2, const float* v2,
+                                 float* out, float* lse, int B, int heads, int N, int M1, int M2, int dh, int q_stride,
+                                 int kv_stride, float scale, void* stream) {
+    TMF_REQUIRE_PTR(q); TMF_REQUIRE_PTR(k1); TMF_REQUIRE_PTR(v1); TMF_REQUIRE_PTR(k2); TMF_REQUIRE_PTR(v2);
+    TMF_REQUIRE_PTR(out); TMF_REQUIRE_PTR(lse);
+    int rc = check_parts("tmf_xattn_fwd_cat", M1, M2);
+    if (rc) return rc;
+    if ((rc = check_attn("tmf_xattn_fwd_cat", B, heads, N, M1 + M2, dh, q_stride, kv_stride))) return rc;
+    TMF_REQUIRE_ALIGNED(out); TMF_REQUIRE_ALIGNED(q); TMF_REQUIRE_ALIGNED(k1); TMF_REQUIRE_ALIGNED(v1);
+    TMF_REQUIRE_ALIGNED(k2); TMF_REQUIRE_ALIGNED(v2);
+    return xattn_fwd_launch("tmf_xattn_fwd_cat", q, k1, v1, k2, v2, out, lse, B, heads, N, M1 + M2, M1, dh, q_stride,
+                            kv_stride, scale, stream);
 }
 
 extern "C" int tmf_xattn_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse,
@@ -498,20 +568,24 @@ extern "C" int tmf_xattn_bwd(const float* q, const float* k, const float* v, con
     TMF_REQUIRE(dkv_stride >= heads * dh && dkv_stride % 4 == 0 && (heads * dh) % 4 == 0, TMF_E_SHAPE,
                 "tmf_xattn_bwd: dkv_stride must be a multiple of 4 and >= heads*dh");
     TMF_REQUIRE_ALIGNED(dq); TMF_REQUIRE_ALIGNED(dk); TMF_REQUIRE_ALIGNED(dv);
-    const int sbk = resident_rows(M, dh), sbq = resident_rows(N, dh);
-    const size_t lds_q = lds_two(sbk, dh), lds_kv = lds_dkv(sbq, dh);
-    hipStream_t s = (hipStream_t)stream;
-#define CALL(DH)                                                                                          \
-    auto k1 = xattn_bwd_dq_kernel<DH>;                                                                    \
-    auto k2 = xattn_bwd_dkv_kernel<DH>;                                                                   \
-    if ((rc = tmf_allow_lds(k1, lds_q, "tmf_xattn_bwd"))) return rc;                                      \
-    if ((rc = tmf_allow_lds(k2, lds_kv, "tmf_xattn_bwd"))) return rc;                                     \
-    hipLaunchKernelGGL(k1, dim3(tmf_cdiv(N, 64), heads, B), dim3(256), lds_q, s, q, k, v, out, lse, dout, dq, \
-                       heads, N, M, q_stride, kv_stride, scale, sbk);                                     \
-    if ((rc = tmf_launch_result("tmf_xattn_bwd(dq)"))) return rc;                                         \
-    hipLaunchKernelGGL(k2, dim3(tmf_cdiv(M, 64), heads, B), dim3(256), lds_kv, s, q, k, v, out, lse, dout, dk, dv, \
-                       heads, N, M, q_stride, kv_stride, dkv_stride, scale, sbq);
-    TMF_DH_SWITCH(dh, CALL)
-#undef CALL
-    return tmf_launch_result("tmf_xattn_bwd(dkv)");
+    return xattn_bwd_launch("tmf_xattn_bwd", q, k, v, k, v, out, lse, dout, dq, dk, dv, dk, dv, B, heads, N, M, M, dh,
+                            q_stride, kv_stride, dkv_stride, scale, stream);
+}
+
+extern "C" int tmf_xattn_bwd_cat(const float* q, const float* k1, const float* v1, const float* k2, const float* v2,
+                                 const float* out, const float* lse, const float* dout, float* dq, float* dk1, float* dv1,
+                                 float* dk2, float* dv2, int B, int heads, int N, int M1, int M2, int dh, int q_stride,
+                                 int kv_stride, int dkv_stride, float scale, void* stream) {
+    TMF_REQUIRE_PTR(q); TMF_REQUIRE_PTR(k1); TMF_REQUIRE_PTR(v1); TMF_REQUIRE_PTR(k2); TMF_REQUIRE_PTR(v2);
+    TMF_REQUIRE_PTR(out); TMF_REQUIRE_PTR(lse); TMF_REQUIRE_PTR(dout); TMF_REQUIRE_PTR(dq);
+    TMF_REQUIRE_PTR(dk1); TMF_REQUIRE_PTR(dv1); TMF_REQUIRE_PTR(dk2); TMF_REQUIRE_PTR(dv2);
+    int rc = check_parts("tmf_xattn_bwd_cat", M1, M2);
+    if (rc) return rc;
+    if ((rc = check_attn("tmf_xattn_bwd_cat", B, heads, N, M1 + M2, dh, q_stride, kv_stride))) return rc;
+    TMF_REQUIRE(dkv_stride >= heads * dh && dkv_stride % 4 == 0 && (heads * dh) % 4 == 0, TMF_E_SHAPE,
+                "tmf_xattn_bwd_cat: dkv_stride must be a multiple of 4 and >= heads*dh");
+    TMF_REQUIRE_ALIGNED(dq); TMF_REQUIRE_ALIGNED(dk1); TMF_REQUIRE_ALIGNED(dv1); TMF_REQUIRE_ALIGNED(dk2);
+    TMF_REQUIRE_ALIGNED(dv2);
+    return xattn_bwd_launch("tmf_xattn_bwd_cat", q, k1, v1, k2, v2, out, lse, dout, dq, dk1, dv1, dk2, dv2, B, heads, N,
+                            M1 + M2, M1, dh, q_stride, kv_stride, dkv_stride, scale, stream);
 }

@@ -1,7 +1,9 @@
 """Drop-in model classes (reference: models/mymodel.py): same constructor arguments, forward
 signatures, return tuples, attribute names and state_dict keys as the reference's ``model_ad``
 (:182-222), ``model_CNN_ad`` (:144-179) and ``model_single`` (:13-37), computed by the MI355X
-HIP kernels.  ``kfold_train_adversarial.py``'s train_step/val_step run unchanged on them.
+HIP kernels.  ``kfold_train_adversarial.py``'s train_step/val_step run unchanged on them.  The paper's
+ablations ``model_CNN`` (:40-66), ``model_transformer`` (:69-98) and ``model_transformer_res`` (:101-141)
+return the logits only, as the reference's do.
 
 The small dense heads (``D``, ``fc_cls``, ``fc``: (B, <=512) matrices) stay on stock torch ops.
 """
@@ -11,7 +13,7 @@ import torch
 from torch import nn
 
 from .gradient_reversal import revgrad
-from .networks import CrossTransformer_MOD_AVG, device_guard, sNet
+from .networks import CrossTransformer, CrossTransformer_MOD_AVG, _TokenReduce, device_guard, sNet
 
 
 def _init_like_reference(module: nn.Module) -> None:
@@ -314,3 +316,70 @@ class model_ad(_FastModeSwitch, nn.Module):
         D_MRI_logits = self.D(revgrad(mri_tok.mean(dim=1), 2.0))
         D_PET_logits = self.D(revgrad(pet_tok.mean(dim=1), 2.0))
         return self.fc_cls(self.fuse_transformer(mri_tok, pet_tok)), D_MRI_logits, D_PET_logits
+
+
+class model_CNN(_FastModeSwitch, nn.Module):
+    """Both encoders, no fusion, no discriminator (mymodel.py:40-66): fc(cat[mean mri, mean pet]) -> logits."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.mri_cnn = sNet(dim)
+        self.pet_cnn = sNet(dim)
+        self.transform = nn.Sequential(nn.AdaptiveAvgPool3d(1), _Flatten5())
+        self.fc = nn.Sequential(nn.Linear(dim * 2, 128), nn.ReLU(), nn.Linear(128, 2))
+        _init_like_reference(self)
+
+    @device_guard
+    def forward(self, mri, pet):
+        mri_emb, pet_emb = _two_streams(self.mri_cnn, mri, self.pet_cnn, pet)
+        mri_tok, pet_tok = _tokens(mri_emb), _tokens(pet_emb)
+        if _cnn_heads_one_call_ok(self, self.fc, None, mri_tok, 2):
+            return _cnn_heads(self, self.fc, None, mri_tok, pet_tok)        # tmf_heads_cnn with M = 2, no discriminator
+        return self.fc(torch.cat([mri_tok.mean(dim=1), pet_tok.mean(dim=1)], dim=1))   # == transform + cat
+
+
+class model_transformer(_FastModeSwitch, nn.Module):
+    """model_ad without the discriminator (mymodel.py:69-98): fc_cls(CrossTransformer_MOD_AVG(tokens)) -> logits.  The fusion
+    block takes the one-call path as model_ad's does; fc_cls runs on stock torch ops (the module path of model_ad's heads)."""
+
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout):
+        super().__init__()
+        self.mri_cnn = sNet(dim)
+        self.pet_cnn = sNet(dim)
+        self.fuse_transformer = CrossTransformer_MOD_AVG(dim, depth, heads, dim_head, mlp_dim, dropout)
+        self.fc_cls = nn.Sequential(nn.Linear(dim * 4, 512), nn.BatchNorm1d(512), nn.ReLU(), nn.Dropout(0.5),
+                                    nn.Linear(512, 64), nn.BatchNorm1d(64), nn.ReLU(), nn.Dropout(0.5),
+                                    nn.Linear(64, 2))
+        _init_like_reference(self)
+
+    @device_guard
+    def forward(self, mri, pet):
+        mri_emb, pet_emb = _two_streams(self.mri_cnn, mri, self.pet_cnn, pet)
+        return self.fc_cls(self.fuse_transformer(_tokens(mri_emb), _tokens(pet_emb)))
+
+
+class model_transformer_res(_FastModeSwitch, nn.Module):
+    """The second fusion design (mymodel.py:101-141): CrossTransformer over both streams' tokens, a second residual
+    (fused + tokens, per stream), the token means of both -> fc_cls (no BatchNorm1d, no discriminator) -> logits.
+    fc_cls runs on stock torch ops."""
+
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout):
+        super().__init__()
+        self.mri_cnn = sNet(dim)
+        self.pet_cnn = sNet(dim)
+        self.fuse_transformer = CrossTransformer(dim, depth, heads, dim_head, mlp_dim, dropout)
+        self.fc_cls = nn.Sequential(nn.Linear(dim * 2, 512), nn.ReLU(), nn.Dropout(0.5),
+                                    nn.Linear(512, 64), nn.ReLU(), nn.Dropout(0.5),
+                                    nn.Linear(64, 2))
+        # attribute parity with mymodel.py:111-116 (parameter-free: 'b n d' -> mean / max over n -> 'b d')
+        self.gap = _TokenReduce("mean")
+        self.gmp = _TokenReduce("max")
+        _init_like_reference(self)
+
+    @device_guard
+    def forward(self, mri, pet):
+        mri_emb, pet_emb = _two_streams(self.mri_cnn, mri, self.pet_cnn, pet)
+        mri_tok, pet_tok = _tokens(mri_emb), _tokens(pet_emb)
+        mri_fused, pet_fused = self.fuse_transformer(mri_tok, pet_tok)
+        cls = torch.cat([self.gap(mri_fused + mri_tok), self.gap(pet_fused + pet_tok)], dim=1)
+        return self.fc_cls(cls)

@@ -248,9 +248,11 @@ class Transformer(nn.Module):
         return [tuple(mk[3 * i:3 * i + 3]) for i in range(len(self.layers))]
 
     @device_guard
-    def forward(self, x, context=None, residual=None):
+    def forward(self, x, context=None, residual=None, context2=None):
         """``residual`` (optional) is added to the result inside the final LayerNorm pass — the caller's
-        ``enc(tokens, context) + tokens`` (reference networks.py:262-263) without a separate kernel."""
+        ``enc(tokens, context) + tokens`` (reference networks.py:262-263) without a separate kernel.  ``context2``
+        (optional, with a context): the keys / values come from [context ; context2] (CrossTransformer,
+        networks.py:250-251), read from the two tensors in place on the token-GEMM path."""
         # The fused layer reads keys / values from an UN-normalised context — what PreNorm hands the attention when
         # a context is passed (networks.py:120-121).  Without one the reference attends over LayerNorm(x) of the
         # CURRENT layer (networks.py:162 `default(context, x)` sees the normalised x), which the op-per-launch
@@ -258,8 +260,10 @@ class Transformer(nn.Module):
         if context is not None and self._fused(x):
             masks = self._keep_masks(x) if self._dropout_active() else [None] * len(self.layers)
             for (attn, ff), mk in zip(self.layers, masks):
-                x = ops.transformer_layer(x, context, attn.norm, attn.fn, ff.norm, ff.fn, mk)
+                x = ops.transformer_layer(x, context, attn.norm, attn.fn, ff.norm, ff.fn, mk, context2)
         else:
+            if context2 is not None:
+                context = torch.cat([context, context2], dim=1)
             for attn, ff in self.layers:
                 x = attn(x, context=context) + x
                 x = ff(x) + x
@@ -340,3 +344,34 @@ class CrossTransformer_MOD_AVG(nn.Module):
             mri_tokens = mri_enc(mri_tokens, context=pet_tokens) + mri_tokens
             pet_tokens = pet_enc(pet_tokens, context=mri_tokens) + pet_tokens
         return ops.token_pool(mri_tokens, pet_tokens)
+
+
+class CrossTransformer(nn.Module):
+    """``depth`` x [mri <- Transformer(mri | [mri ; pet]) + mri ; pet <- Transformer(pet | [NEW mri ; pet]) + pet] ->
+    (mri_tokens, pet_tokens), each (B, N, dim).   reference: networks.py:233-252
+
+    Every instance attends over the tokens of BOTH streams (2 N keys, queries from its own stream).  On the token-GEMM
+    path (ops.TransformerLayer) the two streams stay two tensors: one to_kv launch each, and the attention kernels read
+    keys / values from both in place (tmf_xattn_fwd_cat / _bwd_cat) — no concatenated copy forward or backward.
+    share=True builds one Transformer per layer (the reference's keys); the reference's forward cannot unpack it and
+    raises TypeError, and so does this one."""
+
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout, share=False):
+        super().__init__()
+        self.share = share
+        self.layers = nn.ModuleList([])
+        if self.share == True:      # noqa: E712  (the reference's test, networks.py:238)
+            for _ in range(depth):
+                self.layers.append(Transformer(dim, 1, heads, dim_head, mlp_dim, dropout=dropout))
+        else:
+            for _ in range(depth):
+                self.layers.append(nn.ModuleList([Transformer(dim, 1, heads, dim_head, mlp_dim, dropout=dropout),
+                                                  Transformer(dim, 1, heads, dim_head, mlp_dim, dropout=dropout)]))
+
+    @device_guard
+    def forward(self, mri_tokens, pet_tokens):
+        for mri_enc, pet_enc in self.layers:
+            # context = cat([mri, pet], 1) (networks.py:250-251), handed over as its two parts
+            mri_tokens = mri_enc(mri_tokens, context=mri_tokens, context2=pet_tokens) + mri_tokens
+            pet_tokens = pet_enc(pet_tokens, context=mri_tokens, context2=pet_tokens) + pet_tokens
+        return mri_tokens, pet_tokens

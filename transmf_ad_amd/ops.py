@@ -970,10 +970,13 @@ class TransformerLayer(torch.autograd.Function):
     (to_q with LayerNorm prologue, to_kv, attention, to_out + bias + x, Linear + bias + GELU with LayerNorm
     prologue, Linear + bias + x) and 7 + 1 (all five weight gradients) + 2 reductions backward.  masks = the scaled
     Dropout keep-masks (m_o (R, dim), m_g (R, mlp), m_f (R, dim); any may be None) of networks.py:153, :131, :133, applied
-    in the Linears' epilogues; backward multiplies its incoming gradient by m_f in one extra launch (tmf_mask_mul)."""
+    in the Linears' epilogues; backward multiplies its incoming gradient by m_f in one extra launch (tmf_mask_mul).
+    context2 (optional): the second part of a two-part context [context ; context2] (CrossTransformer, networks.py:250-251),
+    never concatenated: one to_kv launch per part, tmf_xattn_fwd_cat / _bwd_cat read and write both in place."""
 
     @staticmethod
-    def forward(ctx, x, context, g1, b1n, wq, wkv, wo, bo, g2, b2n, w1, b1, w2, b2, heads, scale, eps1, eps2, masks=None):
+    def forward(ctx, x, context, g1, b1n, wq, wkv, wo, bo, g2, b2n, w1, b1, w2, b2, heads, scale, eps1, eps2, masks=None,
+                context2=None):
         mo, mg, mf = masks if masks is not None else (None, None, None)
         x, context = _chk(x, "x"), _chk(context, "context")
         B, N, dim = x.shape
@@ -985,22 +988,35 @@ class TransformerLayer(torch.autograd.Function):
         dh = inner // heads
         out = torch.empty((B * N, inner), device=x.device, dtype=_f32)
         lse = torch.empty((B, heads, N), device=x.device, dtype=_f32)
-        _lib.call("tmf_xattn_fwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, out.data_ptr(),
-                  lse.data_ptr(), B, heads, N, M, dh, inner, 2 * inner, float(scale), _stream())
+        c22d = kv2 = None
+        M2 = 0
+        if context2 is None:
+            _lib.call("tmf_xattn_fwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, out.data_ptr(),
+                      lse.data_ptr(), B, heads, N, M, dh, inner, 2 * inner, float(scale), _stream())
+        else:
+            context2 = _chk(context2, "context2")
+            M2 = context2.shape[1]
+            if context2.shape[0] != B or context2.shape[2] != dim:
+                raise _lib.TmfError(f"context parts {tuple(context.shape)} and {tuple(context2.shape)}")
+            c22d = context2.view(B * M2, dim)
+            kv2, _, _ = tok_linear_fwd(c22d, wkv)
+            _lib.call("tmf_xattn_fwd_cat", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, kv2.data_ptr(),
+                      kv2.data_ptr() + inner * 4, out.data_ptr(), lse.data_ptr(), B, heads, N, M, M2, dh, inner, 2 * inner,
+                      float(scale), _stream())
         x1, _, _ = tok_linear_fwd(out, wo, bias=bo, residual=x2d, mask=mo)
         g, (mean2, rstd2, f), h = tok_linear_fwd(x1, w1, bias=b1, ln=(g2, b2n, eps2), gelu=True, keep_ln_out=True, mask=mg)
         x2, _, _ = tok_linear_fwd(g, w2, bias=b2, residual=x1, mask=mf)
         ctx.save_for_backward(x2d, c2d, g1, wq, wkv, wo, g2, w1, w2, mean1, rstd1, a, q, kv, out, lse, x1, mean2,
-                              rstd2, f, h, g)
-        ctx.cfg = (B, N, M, dim, inner, heads, float(scale))
+                              rstd2, f, h, g, c22d, kv2)
+        ctx.cfg = (B, N, M, dim, inner, heads, float(scale), M2)
         ctx.masks = (mo, mg, mf)
         return x2.view(B, N, dim)
 
     @staticmethod
     def backward(ctx, dx2):
         (x2d, c2d, g1, wq, wkv, wo, g2, w1, w2, mean1, rstd1, a, q, kv, out, lse, x1, mean2, rstd2, f, h,
-         g) = ctx.saved_tensors
-        B, N, M, dim, inner, heads, scale = ctx.cfg
+         g, c22d, kv2) = ctx.saved_tensors
+        B, N, M, dim, inner, heads, scale, M2 = ctx.cfg
         mlp = w1.shape[0]
         R = B * N
         dx2 = _chk(dx2, "grad_output").view(R, dim)
@@ -1023,30 +1039,45 @@ class TransformerLayer(torch.autograd.Function):
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         dhd = inner // heads
-        _lib.call("tmf_xattn_bwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, out.data_ptr(),
-                  lse.data_ptr(), dout.data_ptr(), dq.data_ptr(), dkv.data_ptr(), dkv.data_ptr() + inner * 4,
-                  B, heads, N, M, dhd, inner, 2 * inner, 2 * inner, scale, _stream())
+        dkv2 = dctx2 = None
+        if kv2 is None:
+            _lib.call("tmf_xattn_bwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, out.data_ptr(),
+                      lse.data_ptr(), dout.data_ptr(), dq.data_ptr(), dkv.data_ptr(), dkv.data_ptr() + inner * 4,
+                      B, heads, N, M, dhd, inner, 2 * inner, 2 * inner, scale, _stream())
+        else:
+            dkv2 = torch.empty_like(kv2)
+            _lib.call("tmf_xattn_bwd_cat", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + inner * 4, kv2.data_ptr(),
+                      kv2.data_ptr() + inner * 4, out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dq.data_ptr(),
+                      dkv.data_ptr(), dkv.data_ptr() + inner * 4, dkv2.data_ptr(), dkv2.data_ptr() + inner * 4,
+                      B, heads, N, M, M2, dhd, inner, 2 * inner, 2 * inner, scale, _stream())
+            if ctx.needs_input_grad[19]:
+                dctx2 = tok_linear_bwd_input(dkv2, wkv).view(B, M2, dim)
         dctx = tok_linear_bwd_input(dkv, wkv) if ctx.needs_input_grad[1] else None
         dx = tok_linear_bwd_input(dq, wq, ln=(x2d, mean1, rstd1, g1), add1=dx1, ln_partial=(part, o_ln1),
                                   partial_stride=stride)
         sums = torch.empty(stride, device=dx2.device, dtype=_f32)
         _lib.call("tmf_colsum_finalize", part.data_ptr(), nblk, stride, sums.data_ptr(), _stream())
-        dw2, dw1, dwo, dwkv, dwq = tok_wgrad_multi([(ef, g), (dh_, f), (eo, out), (dkv, c2d), (dq, a)])
+        pairs = [(ef, g), (dh_, f), (eo, out), (dkv, c2d), (dq, a)] + ([] if kv2 is None else [(dkv2, c22d)])
+        dws = tok_wgrad_multi(pairs)
+        dw2, dw1, dwo, dwkv, dwq = dws[:5]
+        if kv2 is not None:
+            dwkv = dwkv + dws[5]                    # to_kv saw both context parts
         return (dx.view(B, N, dim), None if dctx is None else dctx.view(B, M, dim),
                 sums[o_ln1:o_ln1 + dim], sums[o_ln1 + dim:o_ln1 + 2 * dim], dwq, dwkv, dwo, sums[o_bo:o_bo + dim],
                 sums[o_ln2:o_ln2 + dim], sums[o_ln2 + dim:o_ln2 + 2 * dim], dw1, sums[o_b1:o_b1 + mlp], dw2,
-                sums[o_b2:o_b2 + dim], None, None, None, None, None)
+                sums[o_b2:o_b2 + dim], None, None, None, None, None, dctx2)
 
 
-def transformer_layer(x, context, ln1, attn, ln2, ff, masks=None):
+def transformer_layer(x, context, ln1, attn, ln2, ff, masks=None, context2=None):
     """ln1 / ln2: nn.LayerNorm; attn: networks.Attention; ff: networks.FeedForward (parameter containers); masks: the
-    layer's scaled Dropout keep-masks (to_out, after GELU, after the second Linear) or None."""
+    layer's scaled Dropout keep-masks (to_out, after GELU, after the second Linear) or None; context2: the second part of
+    a two-part context [context ; context2] or None."""
     if masks is not None and all(m is None for m in masks):
         masks = None
     return TransformerLayer.apply(x, context, ln1.weight, ln1.bias, attn.to_q.weight, attn.to_kv.weight,
                                   attn.to_out[0].weight, attn.to_out[0].bias, ln2.weight, ln2.bias,
                                   ff.net[0].weight, ff.net[0].bias, ff.net[3].weight, ff.net[3].bias,
-                                  attn.heads, attn.scale, ln1.eps, ln2.eps, masks)
+                                  attn.heads, attn.scale, ln1.eps, ln2.eps, masks, context2)
 
 
 # --------------------------------------------------------------------------------------
