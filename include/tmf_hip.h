@@ -707,6 +707,37 @@ int    tmf_adam_step(int n, float* const* params, const float* const* grads, con
                      float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
                      double weight_decay, int step, void* stream);
 
+/* ---- losses (csrc/losses.hip) -------------------------------------------------------------------------------------
+ * FALoss, reference models/losses.py:122-128: two (B, N, N) similarity matrices F^T F (N = h*w*d tokens of a
+ * (B, C, h, w, d) map), their difference D and F.l1_loss over it.  Here D is formed tile by tile on the matrix pipe and never
+ * written.  f1, f2: fp32 maps of B samples, channels_last == 0: [B][C][N] (NCDHW-contiguous), != 0: [B][N][C] (the
+ * storage behind this library's sNet output).  reduction: 0 'mean' (sum |D| / (B N^2)), 1 'sum'.  loss: one float.
+ * g1, g2 (both or neither; NULL: no gradient wanted): the UNSCALED gradients F1 sign(D) and -F2 sign(D) in the layout of
+ * the inputs; tmf_faloss_bwd turns them into d1 = g1 * 2 grad_out[0] / (B N^2), d2 likewise ('sum': no divisor),
+ * grad_out a device scalar.  The forward of a training step costs 2x the products of a no-grad one and the backward
+ * none; recomputing D in the backward would cost 3x in all.  workspace: tmf_faloss_workspace_bytes(B, N) bytes, 8-byte
+ * aligned: tmf_faloss_partial_rows(B, N) per-workgroup partial sums (double), reduced in a fixed order.
+ * tmf_faloss_ok: 1 when (C, N, reduction) takes the kernels: C a multiple of 32 up to 256, N >= 1, C * N < 2^31.
+ * Two launches forward, one backward. */
+int    tmf_faloss_ok(int C, int N, int reduction);
+int    tmf_faloss_partial_rows(int B, int N);
+size_t tmf_faloss_workspace_bytes(int B, int N);
+int    tmf_faloss_fwd(const float* f1, const float* f2, float* loss, float* g1, float* g2, void* workspace,
+                      size_t workspace_bytes, int B, int C, int N, int channels_last, int reduction, void* stream);
+int    tmf_faloss_bwd(const float* g1, const float* g2, const float* grad_out, float* d1, float* d2, int B, int C, int N,
+                      int reduction, void* stream);
+/* SupConLoss, reference models/losses.py:59-100: features [bs][views][d] fp32 contiguous; contrast row views-major
+ * (row v * bs + s = features[s][v]); anchors: all rows (anchors_all != 0, contrast_mode 'all') or the bs rows of view 0
+ * ('one').  Positives: labels (int64 [bs], device) equal, or mask (float [bs][bs], device, may be asymmetric), or with
+ * both NULL the identity (SimCLR); the self column is excluded from positives and from the log-sum-exp.  An anchor without
+ * a positive gives NaN, as the formula does.  loss: one float.  gfeat (NULL: none): dloss/dfeatures for grad_out = 1;
+ * tmf_supcon_bwd scales it by the device scalar grad_out[0].  tmf_supcon_ok: 1 when bs * views <= 128 and d % 4 == 0.
+ * One launch each, one workgroup. */
+int    tmf_supcon_ok(int bs, int views, int d);
+int    tmf_supcon_fwd(const float* features, const long long* labels, const float* mask, float* loss, float* gfeat,
+                      int bs, int views, int d, int anchors_all, float temperature, float base_temperature, void* stream);
+int    tmf_supcon_bwd(const float* gfeat, const float* grad_out, float* dfeat, int bs, int views, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

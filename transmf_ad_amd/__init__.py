@@ -16,6 +16,7 @@ from .ops import get_conv_precision, set_activation_storage, set_conv_precision 
 from .pipeline import DevicePrefetcher, scale_intensity_flip, rotate_zoom         # noqa: F401
 from .nifti import read_nifti, write_nifti, nifti_batches         # noqa: F401
 from . import optim                                                  # noqa: F401
+from .losses import FALoss, SupConLoss                               # noqa: F401
 from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, FeedForward, PreNorm,   # noqa: F401
                        Transformer, sNet)
 
@@ -23,4 +24,4 @@ __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_trans
            "CrossTransformer", "CrossTransformer_MOD_AVG", "Transformer",
            "Attention", "PreNorm", "FeedForward", "revgrad", "GradientReversal", "load_library", "TmfError",
            "set_conv_precision", "get_conv_precision", "set_activation_storage", "DevicePrefetcher", "scale_intensity_flip", "rotate_zoom",
-           "read_nifti", "write_nifti", "nifti_batches"]
+           "read_nifti", "write_nifti", "nifti_batches", "FALoss", "SupConLoss"]

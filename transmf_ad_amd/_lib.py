@@ -243,6 +243,17 @@ PROTOTYPES.update({
                                C.POINTER(HeadsCnnGrads), _p, _p, _f, _p, _z, _p]),
 })
 
+PROTOTYPES.update({
+    "tmf_faloss_ok": (_i, [_i, _i, _i]),
+    "tmf_faloss_partial_rows": (_i, [_i, _i]),
+    "tmf_faloss_workspace_bytes": (_z, [_i, _i]),
+    "tmf_faloss_fwd": (_i, [_p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
+    "tmf_faloss_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "tmf_supcon_ok": (_i, [_i, _i, _i]),
+    "tmf_supcon_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
+    "tmf_supcon_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+})
+
 _lib = None
 
 

@@ -1484,3 +1484,72 @@ class TokenPool(torch.autograd.Function):
 
 def token_pool(mri, pet):
     return TokenPool.apply(mri, pet)
+
+
+# --------------------------------------------------------------------------------------
+# losses                                                          (losses.py:59-100, 122-128)
+# --------------------------------------------------------------------------------------
+
+class FALossFn(torch.autograd.Function):
+    """sum |F1^T F1 - F2^T F2| (reduction 0: / (B N^2)) over two fp32 maps of one layout: (B, C, N) contiguous
+    (channels_last False) or (B, N, C) contiguous (the storage behind sNet's output).  The forward of a call that wants a
+    gradient also leaves the unscaled gradients (tmf_faloss_fwd); the backward scales them by grad_output."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, B, C, N, channels_last, reduction):
+        f1, f2 = _chk(f1, "feature_map1"), _chk(f2, "feature_map2")
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss = torch.empty((), device=f1.device, dtype=_f32)
+        ws = torch.empty(_lib.query("tmf_faloss_partial_rows", B, N), device=f1.device, dtype=torch.float64)
+        g1 = torch.empty_like(f1) if want else None
+        g2 = torch.empty_like(f2) if want else None
+        _lib.call("tmf_faloss_fwd", f1.data_ptr(), f2.data_ptr(), loss.data_ptr(), _ptr(g1), _ptr(g2), ws.data_ptr(),
+                  ws.numel() * 8, B, C, N, int(channels_last), reduction, _stream())
+        if want:
+            ctx.save_for_backward(g1, g2)
+        ctx.cfg = (B, C, N, reduction)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g1, g2 = ctx.saved_tensors
+        B, C, N, reduction = ctx.cfg
+        dloss = _chk(dloss, "grad_output")
+        d1, d2 = torch.empty_like(g1), torch.empty_like(g2)
+        _lib.call("tmf_faloss_bwd", g1.data_ptr(), g2.data_ptr(), dloss.data_ptr(), d1.data_ptr(), d2.data_ptr(),
+                  B, C, N, reduction, _stream())
+        return d1, d2, None, None, None, None, None
+
+
+def faloss(f1, f2, B, C, N, channels_last, reduction):
+    return FALossFn.apply(f1, f2, B, C, N, channels_last, reduction)
+
+
+class SupConLossFn(torch.autograd.Function):
+    """SupConLoss over contiguous fp32 features (bs, views, d); labels: int64 (bs,) or None; mask: fp32 (bs, bs) or None."""
+
+    @staticmethod
+    def forward(ctx, features, labels, mask, anchors_all, temperature, base_temperature):
+        features = _chk(features, "features")
+        bs, views, d = features.shape
+        want = ctx.needs_input_grad[0]
+        loss = torch.empty((), device=features.device, dtype=_f32)
+        g = torch.empty_like(features) if want else None
+        _lib.call("tmf_supcon_fwd", features.data_ptr(), _ptr(labels), _ptr(mask), loss.data_ptr(), _ptr(g), bs, views, d,
+                  int(anchors_all), float(temperature), float(base_temperature), _stream())
+        if want:
+            ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (g,) = ctx.saved_tensors
+        bs, views, d = g.shape
+        dloss = _chk(dloss, "grad_output")
+        df = torch.empty_like(g)
+        _lib.call("tmf_supcon_bwd", g.data_ptr(), dloss.data_ptr(), df.data_ptr(), bs, views, d, _stream())
+        return df, None, None, None, None, None
+
+
+def supcon_loss(features, labels, mask, anchors_all, temperature, base_temperature):
+    return SupConLossFn.apply(features, labels, mask, anchors_all, temperature, base_temperature)
