@@ -7,7 +7,7 @@ tools/resources.disassembly_of) that the compiler does not make for us.
 2. store data: a buffer/global store of more than 64 bits whose data registers a vector instruction overwrites in the very
    next slot.  LLVM's hazard recognizer exempts stores with an SGPR soffset; on the MI355X such a pair (buffer_store_dwordx4
    v[70:73] .. s4 offen; v_pk_add_f32 v[70:71], ..) stored a wrong v71 in lanes 12-15 of every row of 16 (round 5: found through
-   the Winograd forward's statistics, fixed with store_guard()).
+   the Winograd forward's statistics, fixed with store_guard() of csrc/tmf_device.h).
 
     python tools/asm_checks.py listing.s [kernel-name-substring]         exit code 1 when something is found
 tests/test_host_cpu.py runs the store check on the disassembly of EVERY built object and the in-flight check on conv3d_wino.o.

@@ -23,15 +23,12 @@
 //
 // Replaces, at /root/reference/models/networks.py:166-174: the three rearranges, einsum
 // 'bhid,bhjd->bhij' * scale, Softmax(dim=-1), einsum 'bhij,bhjd->bhid' and their backward.
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
 constexpr int KC = 4;            // key tiles (of 32) per online-softmax chunk
 constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ int frag_row(int r, int hsel) { return (r & 3) + 8 * (r >> 2) + 4 * hsel; }
 
 // acc[i = LDS row][j] += sum_d lds[row0 + (lane&31)][d] * regs[d/2]   (lane>>5 selects d parity)
 template <int DH>

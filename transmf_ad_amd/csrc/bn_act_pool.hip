@@ -598,12 +598,3 @@ extern "C" int tmf_bn_act_pool_bwd_apply(const float* z, const float* dout, cons
                                          int B, int D, int H, int W, int C, int pool, float slope, void* stream) {
     return tmf_bn_act_pool_bwd_apply_t(z, dout, scale, shift, mean, invstd, coef, dz, B, D, H, W, C, pool, slope, 0, stream);
 }
-
-extern "C" int tmf_colsum_finalize(const float* partial, int nblk, int ncol, float* out, void* stream) {
-    TMF_REQUIRE_PTR(partial); TMF_REQUIRE_PTR(out);
-    TMF_REQUIRE(nblk > 0 && ncol > 0, TMF_E_SHAPE, "tmf_colsum_finalize: nblk=%d ncol=%d", nblk, ncol);
-    const dim3 block(64 * TMF_RED_LANES);
-    hipLaunchKernelGGL(tmf_slab_reduce_kernel, dim3(tmf_cdiv(ncol, 64), 1), block, 0, (hipStream_t)stream,
-                       partial, out, nblk, (long)ncol, nblk, 0, 0);
-    return tmf_launch_result("tmf_colsum_finalize");
-}

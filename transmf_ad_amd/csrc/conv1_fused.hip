@@ -20,7 +20,7 @@
 // Replaces, for networks.py:21-26 (sNet.conv1): aten::conv3d, batch_norm, leaky_relu, max_pool3d and their
 // backward (weight gradient only: the network input needs no gradient, kfold_train_adversarial.py:106).
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
@@ -62,7 +62,6 @@ __device__ __forceinline__ constexpr int tapoff(int tap) {
     return tap >= 27 ? 0 : ((tap / 9) * HH + (tap / 3) % 3) * HW + tap % 3;
 }
 // halo index (tap (0,0,0) corner) of M-tile t's origin, and of fragment row r (lane half 0) relative to it
-__device__ __forceinline__ constexpr int tile_org(int t) { return ((2 * (t >> 2)) * HH + 4 * ((t >> 1) & 1)) * HW + 4 * (t & 1); }
 __device__ __forceinline__ constexpr int row_off(int r) {   // r bits: b0 -> w0, b1 -> h0, b2 -> d0, b3 -> w1
     return (((r >> 2) & 1) * HH + ((r >> 1) & 1)) * HW + 2 * ((r >> 3) & 1) + (r & 1);
 }
@@ -84,19 +83,9 @@ struct Args {
     float slope;
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ tmf_bf16x8 pack8(const float (&v)[8]) {
-    const u32x4 p = {tmf_pack_bf16(v[0], v[1]), tmf_pack_bf16(v[2], v[3]), tmf_pack_bf16(v[4], v[5]), tmf_pack_bf16(v[6], v[7])};
+    const tmf_u32x4 p = {tmf_pack_bf16(v[0], v[1]), tmf_pack_bf16(v[2], v[3]), tmf_pack_bf16(v[4], v[5]), tmf_pack_bf16(v[6], v[7])};
     return __builtin_bit_cast(tmf_bf16x8, p);
-}
-
-// x = h + m + l exactly, each part a bf16 number (low 16 bits zero): h / m by truncation, l = the remaining <= 8 bits
-__device__ __forceinline__ void split3(float x, float& h, float& m, float& l) {
-    h = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xFFFF0000u);
-    const float r = x - h;
-    m = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r) & 0xFFFF0000u);
-    l = r - m;
 }
 
 // BF16 = true: both products run on v_mfma_f32_32x32x16_bf16 (operands rounded to bf16, fp32 accumulation) — the
@@ -145,7 +134,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
             if (SPLIT) {
                 float vh[8], vm[8], vl[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) split3(v[j], vh[j], vm[j], vl[j]);
+                for (int j = 0; j < 8; ++j) split3_trunc(v[j], vh[j], vm[j], vl[j]);
                 bwb[0][m] = pack8(vh); bwb[NIMG > 1 ? 1 : 0][m] = pack8(vm); bwb[NIMG > 2 ? 2 : 0][m] = pack8(vl);
             } else {
                 bwb[0][m] = pack8(v);
@@ -276,7 +265,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
             if (SPLIT) {
                 if (e < NHALO) {
                     float ph, pm, pl;
-                    split3(hv[q], ph, pm, pl);
+                    split3_trunc(hv[q], ph, pm, pl);
                     const unsigned short p16[3] = {(unsigned short)(__builtin_bit_cast(unsigned, ph) >> 16),
                                                    (unsigned short)(__builtin_bit_cast(unsigned, pm) >> 16),
                                                    (unsigned short)(__builtin_bit_cast(unsigned, pl) >> 16)};
@@ -322,7 +311,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
                 pr[r] = *reinterpret_cast<const __attribute__((address_space(3))) unsigned*>((size_t)(tb + 2u * (unsigned)brow_off(r)));
         };
         auto mma = [&](int ti, int m, const unsigned (&pr)[9], int wpart = 0) {
-            const u32x4 av = {pr[4 * m < 9 ? 4 * m : 8], pr[4 * m + 1 < 9 ? 4 * m + 1 : 8],
+            const tmf_u32x4 av = {pr[4 * m < 9 ? 4 * m : 8], pr[4 * m + 1 < 9 ? 4 * m + 1 : 8],
                               pr[4 * m + 2 < 9 ? 4 * m + 2 : 8], pr[4 * m + 3 < 9 ? 4 * m + 3 : 8]};
 #if TMF_C1X_ABL & 2
             asm volatile("" :: "v"(av));
@@ -512,7 +501,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
                                 (size_t)(wt + 2u * (unsigned)((u >> 1) * BPLANE + (u & 1) * BROW + 2 * m)));
 #pragma unroll
                         for (int j = 0; j < 8; ++j) bv[j] = z[8 * m + j];
-                        const u32x4 av = {ad[0], ad[1], ad[2], ad[3]};
+                        const tmf_u32x4 av = {ad[0], ad[1], ad[2], ad[3]};
                         accw = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tmf_bf16x8, av), pack8(bv), accw, 0, 0, 0);
                     }
                 } else {

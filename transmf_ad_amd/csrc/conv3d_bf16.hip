@@ -13,22 +13,11 @@
 //
 // Forward and data-gradient (flipped / transposed weights) of networks.py:28,31,37,40,46.
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// round-to-nearest-even, a -> low half: one v_cvt_pk_bf16_f32 on gfx950 (the integer emulation cost 8 VALU
-// instructions per pair and made the staging of the bf16 kernels VALU-bound, PMC)
-__device__ __forceinline__ unsigned int pack_bf16(float a, float b) {
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned int, v);
-}
 
 constexpr int TD = 4, TH = 8, TW = 8;                 // brick: 256 voxels = 8 waves x one 32-voxel M-tile
 constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;
@@ -115,14 +104,14 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
         //      before its LDS writes; two batches keep the kernel under 128 registers (two workgroups per CU) ----
         auto stage_halo = [&](const int q0, const int q1) {
             f32x4 hreg[IN16 ? 1 : HB];
-            u32x2 hreg16[IN16 ? (NT == 1 ? HV : HB) : 1];
+            tmf_u32x2 hreg16[IN16 ? (NT == 1 ? HV : HB) : 1];
 #pragma unroll
             for (int q = q0; q < q1; ++q) {
                 const int c = c0 + ((tid + q * NTHR) & 7) * 4;
                 const bool ok = hoff[q] >= 0 && c < Cin;
                 if (IN16) {
-                    u32x2 v = {0u, 0u};
-                    if (ok) v = *reinterpret_cast<const u32x2*>(xb16 + hoff[q] + c);
+                    tmf_u32x2 v = {0u, 0u};
+                    if (ok) v = *reinterpret_cast<const tmf_u32x2*>(xb16 + hoff[q] + c);
                     hreg16[q - q0] = v;
                 } else {
                     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -134,13 +123,13 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
             for (int q = q0; q < q1; ++q) {
                 const int e = tid + q * NTHR;
                 if (e < NHALO * 8) {
-                    u32x2 pk;
+                    tmf_u32x2 pk;
                     if (IN16) pk = hreg16[q - q0];
                     else {
                         const f32x4 v = hreg[q - q0];
-                        pk = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+                        pk = tmf_u32x2{tmf_pack_bf16(v[0], v[1]), tmf_pack_bf16(v[2], v[3])};
                     }
-                    *reinterpret_cast<u32x2*>(halo + (e >> 3) * RP + (e & 7) * 4) = pk;
+                    *reinterpret_cast<tmf_u32x2*>(halo + (e >> 3) * RP + (e & 7) * 4) = pk;
                 }
             }
         };
@@ -151,16 +140,16 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
         // loads now run PW stages ahead in registers (in-flight global loads survive the barriers: __syncthreads only
         // waits for LDS traffic), and the stage loop is unrolled so the register slots are static.
         constexpr int PW = NT == 1 ? 6 : 1;           // (two tiles: no registers to spare, classic one-stage prefetch)
-        u32x4 wreg[PW][WV];
+        tmf_u32x4 wreg[PW][WV];
         auto load_w = [&](int st, int slot) {
 #pragma unroll
             for (int q = 0; q < WV; ++q) {
                 const int e = tid + q * NTHR;
                 const int row = e >> 2, piece = e & 3;             // row = tap_in_stage * NB + co
                 const int tap = st * TPS + row / NB, co = n0 + row % NB, ci = c0 + piece * 8;
-                u32x4 v = {0u, 0u, 0u, 0u};
+                tmf_u32x4 v = {0u, 0u, 0u, 0u};
                 if (e < TPS * NB * 4 && co < Cout && ci < Cin)
-                    v = *reinterpret_cast<const u32x4*>(w + ((size_t)tap * Cout + co) * Cin + ci);
+                    v = *reinterpret_cast<const tmf_u32x4*>(w + ((size_t)tap * Cout + co) * Cin + ci);
                 wreg[slot][q] = v;
             }
         };
@@ -169,7 +158,7 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
             for (int q = 0; q < WV; ++q) {
                 const int e = tid + q * NTHR;
                 if (e < TPS * NB * 4)
-                    *reinterpret_cast<u32x4*>(Ws + buf * WSTAGE + (e >> 2) * RP + (e & 3) * 8) = wreg[slot][q];
+                    *reinterpret_cast<tmf_u32x4*>(Ws + buf * WSTAGE + (e >> 2) * RP + (e & 3) * 8) = wreg[slot][q];
             }
         };
         load_w(0, 0);
@@ -196,10 +185,10 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
             for (int tp = 0; tp < TPS; ++tp) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {                      // two k-blocks of 16 channels
-                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(halo + a_lane + stage_off + tp * RP + s * 16);
+                    const tmf_bf16x8 a = *reinterpret_cast<const tmf_bf16x8*>(halo + a_lane + stage_off + tp * RP + s * 16);
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
-                        const bf16x8 bb = *reinterpret_cast<const bf16x8*>(ws + (tp * NB + j * 32) * RP + s * 16);
+                        const tmf_bf16x8 bb = *reinterpret_cast<const tmf_bf16x8*>(ws + (tp * NB + j * 32) * RP + s * 16);
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bb, acc[j], 0, 0, 0);
                     }
                 }
@@ -232,7 +221,7 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
                     const int co = n0 + j * 32 + l31;
                     const float a = acc[j][r], b = acc[j][r + 1];
                     const float other = __shfl_xor(odd ? a : b, 1);       // even lane gets the odd lane's a, odd gets b
-                    const unsigned int pk = odd ? pack_bf16(other, b) : pack_bf16(a, other);
+                    const unsigned int pk = odd ? tmf_pack_bf16(other, b) : tmf_pack_bf16(a, other);
                     if (FULL || (pv && co < Cout))
                         *reinterpret_cast<unsigned int*>(zb16 + off + (co & ~1)) = pk;
                     // statistics: each lane's own channel, both rows (validity of each row separately)
@@ -294,32 +283,9 @@ __global__ __launch_bounds__(NTHR, 4) void conv3d_fwd_bf16_kernel(
 }
 
 
-namespace dma {
-// LDS-DMA of 16 bytes per lane: LDS byte = lds_wave_base (wave-uniform LDS address) + 16 * lane.  Written as inline
-// assembly on purpose: with __builtin_amdgcn_global_load_lds the compiler cannot tell that the copy fills the OTHER
-// buffer and waits vmcnt(0) before the first fragment read of every brick, which serialises copy and multiply (the
-// first build did: 61 us of 240 exposed).  The price is that the compiler does not see the copies at all: the kernel
-// waits for them itself (dma_wait) before the barrier that publishes the buffer.
-__device__ __forceinline__ void glds16(const void* g, unsigned lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_wave_base) : "memory");
-}
-// The same through a buffer resource: LDS byte = lds_wave_base + 16 * lane <- resource base + voff (per lane) + soff (scalar).
-// A lane whose voff + soff is not below the resource's num_records delivers ZEROS to its LDS bytes (gfx950: the scalar
-// offset is part of the range check, tools/microbench/blds_probe.hip) — zero fill costs no pointer select, no compare.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)p;
-    return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ void blds16(int voff, i32x4 rsrc, int soff, unsigned lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rsrc), "s"(soff), "s"(lds_wave_base) : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
 }
-}  // namespace dma
-__device__ __attribute__((aligned(16))) const unsigned int tmf_zero16[4] = {0u, 0u, 0u, 0u};
 
 // ------------------------------------------------------------------------------------------------------------
 // Large-layer variant: 8x8x8 bricks, a 2 x NT REGISTER TILE per wave.
@@ -443,7 +409,6 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
     TR(1);
     if constexpr (DMA) {
         static_assert(IN16, "the DMA form copies bf16 tensors");
-        using namespace dma;
         constexpr int HBYTES = v2::Cfg<NT>::HBYTES, WBYTES = v2::Cfg<NT>::WBYTES;
         constexpr int MT2B = 4 * HH * HW * 32;                 // bytes to the wave's second M-tile (planes 4-7)
         const unsigned lds0 = lds_addr(smem_raw);
@@ -529,12 +494,12 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
             constexpr bool FIRST = decltype(first_c)::value;
             if (!FIRST) __syncthreads();                       // the halo of the previous chunk is read out
             TR(10);
-            if (!wrole) { issue_h(c0); TR(11); dma_wait(); TR(12); }
+            if (!wrole) { issue_h(c0); TR(11); vm_wait<0>(); TR(12); }
 #pragma unroll
             for (int st = 0; st < NSTD; ++st) {
                 const int wb = (st & 1) ^ par;
                 TR(20);
-                if (wrole) dma_wait();                         // this wave's share of stage st has landed ...
+                if (wrole) vm_wait<0>();                       // this wave's share of stage st has landed ...
                 TR(21);
                 __syncthreads();                               // ... everybody's has (and the halo), and stage st - 1 is read out
                 TR(22);
@@ -548,13 +513,13 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
                 // software pipeline over the 9 taps: the fragments of tap tp + 1 are requested BEFORE the products of tap tp
                 // are issued (left to the compiler a fragment was requested one product ahead of its use and every product
                 // had its own s_waitcnt: the waves of a SIMD then sit out the LDS latency together)
-                struct Frag { bf16x8 a0, a1, b[NT]; };
+                struct Frag { tmf_bf16x8 a0, a1, b[NT]; };
                 auto load = [&](int tp, Frag& f) {                                                     // kh = tp / 3, kw = tp % 3
                     const unsigned char* ap = smem_raw + ((st * HH + tp / 3) * HW + tp % 3) * 32 + a_kd[st];   // kd = st
-                    f.a0 = *reinterpret_cast<const bf16x8*>(ap);
-                    f.a1 = *reinterpret_cast<const bf16x8*>(ap + MT2B);
+                    f.a0 = *reinterpret_cast<const tmf_bf16x8*>(ap);
+                    f.a1 = *reinterpret_cast<const tmf_bf16x8*>(ap + MT2B);
 #pragma unroll
-                    for (int j = 0; j < NT; ++j) f.b[j] = *reinterpret_cast<const bf16x8*>(wsb + (tp * NB + j * 32) * 32);
+                    for (int j = 0; j < NT; ++j) f.b[j] = *reinterpret_cast<const tmf_bf16x8*>(wsb + (tp * NB + j * 32) * 32);
                 };
                 auto mul = [&](const Frag& f, bool zero_c) {
 #pragma unroll
@@ -605,36 +570,36 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
         // ---- weight stages: [tap][co][ci] bf16; a stage = 3 taps x NB rows x 16 channels = 2 pieces of 16 B per row ----
         constexpr int NPIECE = TPS * NB * 2;                  // 384 | 192 <= NTHR: one piece per thread
         constexpr int PW = 2;                                 // stages requested ahead, in registers
-        u32x4 wreg[PW];
+        tmf_u32x4 wreg[PW];
         auto load_w = [&](int st, int slot) {
             const int row = tid >> 1, piece = tid & 1;        // row = tap_in_stage * NB + co
             const int col = row % NB;
             const int tap = st * TPS + row / NB, co = n0 + (PERM ? 2 * (col & 31) + (col >> 5) : col), ci = c0 + piece * 8;
-            u32x4 v = {0u, 0u, 0u, 0u};
+            tmf_u32x4 v = {0u, 0u, 0u, 0u};
             if (tid < NPIECE && co < Cout && ci < Cin && !(dbg & 1))
-                v = *reinterpret_cast<const u32x4*>(w + ((size_t)tap * Cout + co) * Cin + ci);
+                v = *reinterpret_cast<const tmf_u32x4*>(w + ((size_t)tap * Cout + co) * Cin + ci);
             wreg[slot] = v;
         };
         auto store_w = [&](int buf, int slot) {
             if (tid < NPIECE)
-                *reinterpret_cast<u32x4*>(Ws + buf * WSTAGE + (tid >> 1) * RP + (tid & 1) * 8) = wreg[slot];
+                *reinterpret_cast<tmf_u32x4*>(Ws + buf * WSTAGE + (tid >> 1) * RP + (tid & 1) * 8) = wreg[slot];
         };
 #pragma unroll
         for (int st = 0; st < PW; ++st) load_w(st, st);
         // ---- halo: all loads of the chunk are issued before the first LDS write ----
         if constexpr (IN16) {
-            u32x4 hreg[HV];
+            tmf_u32x4 hreg[HV];
 #pragma unroll
             for (int q = 0; q < HV; ++q) {
                 const int c = c0 + ((tid + q * NTHR) & 1) * 8;
-                u32x4 v = {0u, 0u, 0u, 0u};
-                if (hoff[q] >= 0 && c < Cin && !(dbg & 2)) v = *reinterpret_cast<const u32x4*>(xb16 + hoff[q] + c);
+                tmf_u32x4 v = {0u, 0u, 0u, 0u};
+                if (hoff[q] >= 0 && c < Cin && !(dbg & 2)) v = *reinterpret_cast<const tmf_u32x4*>(xb16 + hoff[q] + c);
                 hreg[q] = v;
             }
 #pragma unroll
             for (int q = 0; q < HV; ++q) {
                 const int e = tid + q * NTHR;
-                if (e < NHALO * PPP) *reinterpret_cast<u32x4*>(halo + (e >> 1) * RP + (e & 1) * 8) = hreg[q];
+                if (e < NHALO * PPP) *reinterpret_cast<tmf_u32x4*>(halo + (e >> 1) * RP + (e & 1) * 8) = hreg[q];
             }
         } else {
             // fp32 tensors: batches of HB pieces keep the kernel under 128 registers
@@ -653,8 +618,8 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
                 for (int q = q0; q < q0 + HB; ++q) {
                     const int e = tid + q * NTHR;
                     if (e < NHALO * PPP)
-                        *reinterpret_cast<u32x2*>(halo + (e >> 2) * RP + (e & 3) * 4) =
-                            u32x2{pack_bf16(hreg[q - q0][0], hreg[q - q0][1]), pack_bf16(hreg[q - q0][2], hreg[q - q0][3])};
+                        *reinterpret_cast<tmf_u32x2*>(halo + (e >> 2) * RP + (e & 3) * 4) =
+                            tmf_u32x2{tmf_pack_bf16(hreg[q - q0][0], hreg[q - q0][1]), tmf_pack_bf16(hreg[q - q0][2], hreg[q - q0][3])};
                 }
             }
         }
@@ -669,11 +634,11 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
             const u16* ws = Ws + buf * WSTAGE + b_lane;
 #pragma unroll
             for (int tp = 0; tp < TPS; ++tp) {                                            // kw
-                const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ap + tp * RP);
-                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ap + tp * RP + MT2);
+                const tmf_bf16x8 a0 = *reinterpret_cast<const tmf_bf16x8*>(ap + tp * RP);
+                const tmf_bf16x8 a1 = *reinterpret_cast<const tmf_bf16x8*>(ap + tp * RP + MT2);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const bf16x8 bb = *reinterpret_cast<const bf16x8*>(ws + (tp * NB + j * 32) * RP);
+                    const tmf_bf16x8 bb = *reinterpret_cast<const tmf_bf16x8*>(ws + (tp * NB + j * 32) * RP);
                     acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bb, acc[0][j], 0, 0, 0);
                     acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bb, acc[1][j], 0, 0, 0);
                 }
@@ -719,7 +684,7 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
                             const int r = q4 * 4 + pd, gd = d0 + 4 * m + pd;
                             const bool d_ok = FULL || gd < D;                 // wave-uniform
                             float v0 = acc[m][0][r], v1 = acc[m][NT - 1][r];
-                            if (d_ok && !(dbg & 16)) __builtin_amdgcn_raw_buffer_store_b32(pack_bf16(v0, v1), zr, vof, gd * plane, 0);
+                            if (d_ok && !(dbg & 16)) __builtin_amdgcn_raw_buffer_store_b32(tmf_pack_bf16(v0, v1), zr, vof, gd * plane, 0);
                             if constexpr (STATS) {
                                 if (!FULL) { v0 = (lane_ok && d_ok) ? v0 : 0.f; v1 = (lane_ok && d_ok) ? v1 : 0.f; }
                                 s1[0] += v0; s2[0] += v0 * v0;
@@ -734,7 +699,7 @@ __global__ __launch_bounds__(v2::NTHR, 4) void conv3d_fwd_bf16_v2_kernel(
                             for (int pd = 0; pd < 4; pd += 2) {
                                 const int r = q4 * 4 + pd, gd = d0 + 4 * m + pd;      // this lane stores plane gd + odd
                                 float a = acc[m][j][r], bq = acc[m][j][r + 1];
-                                const unsigned own = pack_bf16(a, bq);
+                                const unsigned own = tmf_pack_bf16(a, bq);
                                 const unsigned oth = (unsigned)__builtin_amdgcn_mov_dpp((int)own, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
                                 const unsigned pk = __builtin_amdgcn_perm(oth, own, sel);
                                 int vof = vo + j * 64 + odd * plane;
@@ -849,17 +814,6 @@ constexpr int SWSTAGE = STPS * 32 * SRP;              // bf16 elements per weigh
 constexpr size_t SPLIT_LDS_BYTES = (size_t)(3 * SHALO + 2 * 3 * SWSTAGE) * 2 + 8 * 32 * 2 * 4;
 __device__ __forceinline__ int swz(int row, int half) { return row * SRP + ((half ^ ((row >> 3) & 1)) << 3); }
 
-__device__ __forceinline__ unsigned int rne_bf16_bits(float a) {          // bf16 bit pattern in the low half
-    return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)a);
-}
-__device__ __forceinline__ void split3(float a, unsigned int& h, unsigned int& m, unsigned int& l) {
-    h = rne_bf16_bits(a);
-    const float r1 = a - __builtin_bit_cast(float, h << 16);             // exact
-    m = rne_bf16_bits(r1);
-    const float r2 = r1 - __builtin_bit_cast(float, m << 16);            // exact, fits bf16
-    l = rne_bf16_bits(r2);
-}
-
 __global__ __launch_bounds__(NTHR) void conv3d_fwd_split_kernel(
     const float* __restrict__ x, const u16* __restrict__ w3, float* __restrict__ z,
     float* __restrict__ stat_partial, int D, int H, int W, int Cin, int Cout,
@@ -932,43 +886,39 @@ __global__ __launch_bounds__(NTHR) void conv3d_fwd_split_kernel(
             hreg[q] = v;
         }
         // ---- weights: pre-split on the host, [part][tap][co][ci]; one 16-B piece = 8 input channels ----
-        u32x4 wreg[WV];
+        tmf_u32x4 wreg[WV];
         auto load_w = [&](int st) {
 #pragma unroll
             for (int q = 0; q < WV; ++q) {
-                u32x4 v = {0u, 0u, 0u, 0u};
+                tmf_u32x4 v = {0u, 0u, 0u, 0u};
                 if (woff[q] >= 0 && c0 + (tid & 1) * 8 < Cin)
-                    v = *reinterpret_cast<const u32x4*>(w3 + woff[q] + st * wstage_stride + c0);
+                    v = *reinterpret_cast<const tmf_u32x4*>(w3 + woff[q] + st * wstage_stride + c0);
                 wreg[q] = v;
             }
         };
         auto store_w = [&](int buf) {
 #pragma unroll
             for (int q = 0; q < WV; ++q)
-                if (wdst[q] >= 0) *reinterpret_cast<u32x4*>(Ws + buf * 3 * SWSTAGE + wdst[q]) = wreg[q];
+                if (wdst[q] >= 0) *reinterpret_cast<tmf_u32x4*>(Ws + buf * 3 * SWSTAGE + wdst[q]) = wreg[q];
         };
         load_w(0);
 #pragma unroll
         for (int q = 0; q < HV; ++q) {
             if (hdst[q] >= 0) {
-                // exact 3-way split by truncation: a = hi + mid + lo, each with <= 8 significand bits
                 unsigned int hh_[4], mm_[4], ll_[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float a = hreg[q][u];
-                    const unsigned int hb = __builtin_bit_cast(unsigned int, a) & 0xFFFF0000u;
-                    const float r1 = a - __builtin_bit_cast(float, hb);
-                    const unsigned int mb = __builtin_bit_cast(unsigned int, r1) & 0xFFFF0000u;
-                    const float r2 = r1 - __builtin_bit_cast(float, mb);
-                    hh_[u] = hb; mm_[u] = mb; ll_[u] = __builtin_bit_cast(unsigned int, r2);
+                    float h, m, l;
+                    split3_trunc(hreg[q][u], h, m, l);
+                    hh_[u] = __builtin_bit_cast(unsigned int, h); mm_[u] = __builtin_bit_cast(unsigned int, m); ll_[u] = __builtin_bit_cast(unsigned int, l);
                 }
                 u16* dst = halo + hdst[q];
-                u32x2 ph = {(hh_[0] >> 16) | hh_[1], (hh_[2] >> 16) | hh_[3]};
-                u32x2 pm = {(mm_[0] >> 16) | mm_[1], (mm_[2] >> 16) | mm_[3]};
-                u32x2 pl = {(ll_[0] >> 16) | (ll_[1] & 0xFFFF0000u), (ll_[2] >> 16) | (ll_[3] & 0xFFFF0000u)};
-                *reinterpret_cast<u32x2*>(dst) = ph;
-                *reinterpret_cast<u32x2*>(dst + SHALO) = pm;
-                *reinterpret_cast<u32x2*>(dst + 2 * SHALO) = pl;
+                tmf_u32x2 ph = {(hh_[0] >> 16) | hh_[1], (hh_[2] >> 16) | hh_[3]};
+                tmf_u32x2 pm = {(mm_[0] >> 16) | mm_[1], (mm_[2] >> 16) | mm_[3]};
+                tmf_u32x2 pl = {(ll_[0] >> 16) | (ll_[1] & 0xFFFF0000u), (ll_[2] >> 16) | (ll_[3] & 0xFFFF0000u)};
+                *reinterpret_cast<tmf_u32x2*>(dst) = ph;
+                *reinterpret_cast<tmf_u32x2*>(dst + SHALO) = pm;
+                *reinterpret_cast<tmf_u32x2*>(dst + 2 * SHALO) = pl;
             }
         }
         for (int st = 0; st < SNST; ++st) {                     // stage = kd plane (9 taps)
@@ -978,15 +928,15 @@ __global__ __launch_bounds__(NTHR) void conv3d_fwd_split_kernel(
             if (st + 1 < SNST) load_w(st + 1);
             const u16* ws = Ws + buf * 3 * SWSTAGE;
             // explicit software pipeline: the six fragments of tap t+1 are in flight while tap t multiplies
-            bf16x8 fa[2][3], fb[2][3];
+            tmf_bf16x8 fa[2][3], fb[2][3];
             auto fetch = [&](const int tp, const int slot) {
                 const int arow = a_lane + (st * HH + tp / 3) * HW + tp % 3;
                 const u16* ap = halo + swz(arow, hsel);
                 const u16* bp = ws + swz(tp * 32 + l31, hsel);
 #pragma unroll
                 for (int part = 0; part < 3; ++part) {
-                    fa[slot][part] = *reinterpret_cast<const bf16x8*>(ap + part * SHALO);
-                    fb[slot][part] = *reinterpret_cast<const bf16x8*>(bp + part * SWSTAGE);
+                    fa[slot][part] = *reinterpret_cast<const tmf_bf16x8*>(ap + part * SHALO);
+                    fb[slot][part] = *reinterpret_cast<const tmf_bf16x8*>(bp + part * SWSTAGE);
                 }
             };
             fetch(0, 0);
@@ -994,8 +944,8 @@ __global__ __launch_bounds__(NTHR) void conv3d_fwd_split_kernel(
             for (int tp = 0; tp < STPS; ++tp) {
                 const int cur = tp & 1;
                 if (tp + 1 < STPS) fetch(tp + 1, cur ^ 1);
-                const bf16x8 ah = fa[cur][0], am = fa[cur][1], al = fa[cur][2];
-                const bf16x8 bh = fb[cur][0], bm = fb[cur][1], bl = fb[cur][2];
+                const tmf_bf16x8 ah = fa[cur][0], am = fa[cur][1], al = fa[cur][2];
+                const tmf_bf16x8 bh = fb[cur][0], bm = fb[cur][1], bl = fb[cur][2];
                 // two independent chains: the 2^-16..2^-8 cross terms, and the leading terms
                 acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc2, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
@@ -1178,8 +1128,8 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_kernel(
                         u16* dst = xT + (2 * pr + h) * WG_XP + hrow * 8;
 #pragma unroll
                         for (int sft = 0; sft < 3; ++sft) {
-                            u32x4 o = {pk[sft], pk[sft + 2], pk[sft + 4], pk[sft + 6]};
-                            *reinterpret_cast<u32x4*>(dst + sft * WG_XIMG) = o;
+                            tmf_u32x4 o = {pk[sft], pk[sft + 2], pk[sft + 4], pk[sft + 6]};
+                            *reinterpret_cast<tmf_u32x4*>(dst + sft * WG_XIMG) = o;
                         }
                     }
                 }
@@ -1187,9 +1137,9 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_kernel(
             const int row = tid >> 4;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                u32x4 o = {pair16(dw2[0], dw2[1], h), pair16(dw2[2], dw2[3], h), pair16(dw2[4], dw2[5], h),
+                tmf_u32x4 o = {pair16(dw2[0], dw2[1], h), pair16(dw2[2], dw2[3], h), pair16(dw2[4], dw2[5], h),
                            pair16(dw2[6], dw2[7], h)};
-                *reinterpret_cast<u32x4*>(dzT + (2 * pr + h) * WG_DP + row * 8) = o;
+                *reinterpret_cast<tmf_u32x4*>(dzT + (2 * pr + h) * WG_DP + row * 8) = o;
             }
         } else {
 #pragma unroll
@@ -1198,21 +1148,21 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_kernel(
                 if (hrow < HD * HH) {
                     unsigned int pk[HW - 1];                       // pk[q] = bf16(v[q]) | bf16(v[q+1]) << 16
 #pragma unroll
-                    for (int q = 0; q < HW - 1; ++q) pk[q] = pack_bf16(xv[i][q], xv[i][q + 1]);
+                    for (int q = 0; q < HW - 1; ++q) pk[q] = tmf_pack_bf16(xv[i][q], xv[i][q + 1]);
                     u16* dst = xT + l31 * WG_XP + hrow * 8;
 #pragma unroll
                     for (int sft = 0; sft < 3; ++sft) {
-                        u32x4 o = {pk[sft], pk[sft + 2], pk[sft + 4], pk[sft + 6]};
-                        *reinterpret_cast<u32x4*>(dst + sft * WG_XIMG) = o;
+                        tmf_u32x4 o = {pk[sft], pk[sft + 2], pk[sft + 4], pk[sft + 6]};
+                        *reinterpret_cast<tmf_u32x4*>(dst + sft * WG_XIMG) = o;
                     }
                 }
             }
 #pragma unroll
             for (int i = 0; i < DQ; ++i) {
                 const int row = (tid + i * NTHR) >> 5;
-                u32x4 o = {pack_bf16(dv[i][0], dv[i][1]), pack_bf16(dv[i][2], dv[i][3]), pack_bf16(dv[i][4], dv[i][5]),
-                           pack_bf16(dv[i][6], dv[i][7])};
-                *reinterpret_cast<u32x4*>(dzT + l31 * WG_DP + row * 8) = o;
+                tmf_u32x4 o = {tmf_pack_bf16(dv[i][0], dv[i][1]), tmf_pack_bf16(dv[i][2], dv[i][3]), tmf_pack_bf16(dv[i][4], dv[i][5]),
+                           tmf_pack_bf16(dv[i][6], dv[i][7])};
+                *reinterpret_cast<tmf_u32x4*>(dzT + l31 * WG_DP + row * 8) = o;
             }
         }
     };
@@ -1229,11 +1179,11 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_kernel(
 #pragma unroll 4
             for (int ks = 0; ks < TD * TH / 2; ++ks) {        // 16 voxels per step: brick rows 2*ks and 2*ks + 1
                 const int d = ks / (TH / 2), hp = (ks % (TH / 2)) * 2;
-                const bf16x8 bv = *reinterpret_cast<const bf16x8*>(dzT + b_off + (d * TH + hp) * 8);
+                const tmf_bf16x8 bv = *reinterpret_cast<const tmf_bf16x8*>(dzT + b_off + (d * TH + hp) * 8);
                 const int xrow = (d * HH + hp) * 8;
-                bf16x8 av[NTAPS];
+                tmf_bf16x8 av[NTAPS];
 #pragma unroll
-                for (int t = 0; t < NTAPS; ++t) av[t] = *reinterpret_cast<const bf16x8*>(xT + a_off[t] + xrow);
+                for (int t = 0; t < NTAPS; ++t) av[t] = *reinterpret_cast<const tmf_bf16x8*>(xT + a_off[t] + xrow);
 #pragma unroll
                 for (int t = 0; t < NTAPS; ++t)
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[t], bv, acc[t], 0, 0, 0);
@@ -1282,14 +1232,13 @@ constexpr size_t lds_bytes(int nh) { return (size_t)2 * (XB + nh * DZB); }
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
-__device__ __forceinline__ bf16x8 tr8(const unsigned char* p) {      // voxels 0-3 at p, voxels 4-7 at p + 4 * 64
+__device__ __forceinline__ tmf_bf16x8 tr8(const unsigned char* p) {      // voxels 0-3 at p, voxels 4-7 at p + 4 * 64
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 256));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
+    return __builtin_bit_cast(tmf_bf16x8, v);
 }
-using namespace dma;
 }  // namespace wtr
 
 template <int NH, bool IN16>
@@ -1425,10 +1374,10 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_tr_kernel(
     // requested BEFORE the MFMAs of k-step ks are issued (left to the compiler they were requested behind all but the
     // last two: both waves of a SIMD then sat out the LDS latency together, 50 us of a 240 us launch).  `mid` runs after
     // the second k-step: the copies of the next brick are issued in the shadow of queued MFMAs, not in front of them.
-    struct Frag { bf16x8 a[4]; bf16x8 b[NH]; };
+    struct Frag { tmf_bf16x8 a[4]; tmf_bf16x8 b[NH]; };
     auto load = [&](const unsigned char* base, int ks, Frag& f) {
         if constexpr ((dbg & 2) != 0) {
-            bf16x8 c;
+            tmf_bf16x8 c;
 #pragma unroll
             for (int e = 0; e < 8; ++e) c[e] = (__bf16)(float)(ks + e);
 #pragma unroll
@@ -1458,7 +1407,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_tr_kernel(
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
                     acc[2 * t + n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[t], f.b[n], acc[2 * t + n], 0, 0, 0);
-            const bf16x8 bs = pair ? f.b[1] : f.b[0];
+            const tmf_bf16x8 bs = pair ? f.b[1] : f.b[0];
             acc[6] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[3], bs, acc[6], 0, 0, 0);
         } else {
 #pragma unroll
@@ -1524,11 +1473,11 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_tr_kernel(
         };
         int cur = 0;
         if (tile_begin < tile_end) issue(0);
-        dma_wait();
+        vm_wait<0>();
         __syncthreads();
         for (int tile = tile_begin; tile < tile_end; tile += tile_step) {
             mma(cur, [&]() { if (tile + tile_step < tile_end) issue(cur ^ 1); });
-            dma_wait();                          // this wave's copies of brick n+1 have landed ...
+            vm_wait<0>();                        // this wave's copies of brick n+1 have landed ...
             if (!(dbg & 8)) __syncthreads();     // ... and so have everybody else's
             cur ^= 1;
         }
@@ -1538,12 +1487,12 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_tr_kernel(
         // waves 4-7: multiply, then stage), so the matrix pipe always has a wave feeding it.
         const float* xg = reinterpret_cast<const float*>(x_);
         const float* dg = reinterpret_cast<const float*>(dz_);
-        u32x4 xr[XQ], dr[DQ];
-        auto load8 = [&](const float* p8, bool ok) -> u32x4 {
-            if (!ok) return u32x4{0u, 0u, 0u, 0u};
+        tmf_u32x4 xr[XQ], dr[DQ];
+        auto load8 = [&](const float* p8, bool ok) -> tmf_u32x4 {
+            if (!ok) return tmf_u32x4{0u, 0u, 0u, 0u};
             const float4 a = *reinterpret_cast<const float4*>(p8);
             const float4 b_ = *reinterpret_cast<const float4*>(p8 + 4);
-            return u32x4{pack_bf16(a.x, a.y), pack_bf16(a.z, a.w), pack_bf16(b_.x, b_.y), pack_bf16(b_.z, b_.w)};
+            return tmf_u32x4{tmf_pack_bf16(a.x, a.y), tmf_pack_bf16(a.z, a.w), tmf_pack_bf16(b_.x, b_.y), tmf_pack_bf16(b_.z, b_.w)};
         };
         auto fetch = [&]() {
             const Origin o = origin_next();
@@ -1557,9 +1506,9 @@ __global__ __launch_bounds__(NTHR) void conv3d_wgrad_bf16_tr_kernel(
             unsigned char* base = smem_raw + buf * BUFB + tid * 16;
 #pragma unroll
             for (int i = 0; i < XQ; ++i)
-                if (tid + i * NTHR < XCH) *reinterpret_cast<u32x4*>(base + i * (NTHR * 16)) = xr[i];
+                if (tid + i * NTHR < XCH) *reinterpret_cast<tmf_u32x4*>(base + i * (NTHR * 16)) = xr[i];
 #pragma unroll
-            for (int i = 0; i < DQ; ++i) *reinterpret_cast<u32x4*>(base + XB + i * (NTHR * 16)) = dr[i];
+            for (int i = 0; i < DQ; ++i) *reinterpret_cast<tmf_u32x4*>(base + XB + i * (NTHR * 16)) = dr[i];
         };
         int cur = 0;
         if (tile_begin < tile_end) {

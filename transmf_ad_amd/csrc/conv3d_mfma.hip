@@ -23,7 +23,7 @@
 // Replaces aten::conv3d / convolution_backward at /root/reference/models/networks.py:
 // 22,28,31,37,40,46,49.
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 // kernel A/B switches (builds for TMF_LIB=...): plane-long partial sums, buffer-resource staging
 #ifndef TMF_CONV_ACC
@@ -34,8 +34,6 @@
 #endif
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------------------------
 // forward / dgrad

@@ -36,15 +36,11 @@
 //
 // Replaces aten::conv3d / convolution_backward at /root/reference/models/networks.py:28,31,37,40,46.
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TD = 4, TH = 8, TW = 8;                 // output brick
-constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;  // input halo
 constexpr int CK = 8;                                 // input channels per chunk
 constexpr int NTHR = 512;
 // Halo of one chunk in LDS, in 16-byte slots (4 channels of one voxel).  The two channel quads of a voxel sit side by side (one
@@ -71,27 +67,6 @@ static_assert(B_OFF + B_BYTES <= EX_FLOATS * 4, "LDS carving");
 __device__ __forceinline__ constexpr int ogd(int dd) { return (dd & 1) * 384 + (dd >> 1) * 32; }
 __device__ __forceinline__ constexpr int ogh(int i) { return (i & 1) * 192 + (i >> 1) * 6; }
 __device__ __forceinline__ constexpr int ogw(int k) { return (k & 1) * 96 + (k >> 1); }
-
-// LDS-DMA of 16 bytes per lane through a buffer resource: LDS byte = lds_wave_base + 16 * lane <- base + voff + soff; a
-// lane outside the range delivers zeros (the same helper and the same reasons as conv3d_bf16.hip: the compiler does not
-// see these copies, the kernel waits for them itself before the barrier that publishes the buffer)
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)p;
-    return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ void blds16(int voff, i32x4 rsrc, int soff, unsigned lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rsrc), "s"(soff), "s"(lds_wave_base) : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// A buffer_store_dwordx4 reads its data registers AFTER it has issued: a v_pk_* that overwrites them in the very next slot
-// corrupted the second register of the pair in lanes 12-15 of every row of 16 (measured on gfx950 with an SGPR soffset, the
-// case LLVM's hazard recognizer exempts; tools/asm_checks.py finds the pattern in a listing).  One wait state after a store
-// whose data dies right behind it:
-__device__ __forceinline__ void store_guard() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 0");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 #ifdef TMF_WINO_TRACE
 // instrumented build (tools/wino_trace.py): shader-clock stamps of every block (start, end, hardware ids) and of the phases of one
@@ -200,7 +175,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_wino_kernel(
     const float* Bl = smem + (B_OFF + wave * 8192) / 4 + lane * 4;
     f32x16 acc[8];
     TRP(1);
-    dma_wait();
+    vm_wait<0>();
     __syncthreads();
     TRP(2);
 
@@ -256,7 +231,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_wino_kernel(
         }
     };
     auto sync = [&]() {
-        dma_wait();
+        vm_wait<0>();
         __syncthreads();                            // the next halo and weights are in LDS; every wave is done with the running halo
     };
     if (wave < 4) {
@@ -498,10 +473,7 @@ template <int GEOM> struct PLds {
     static_assert(SLOTS_G % PN == 0 && BYTES <= 160 * 1024, "LDS carving");
 };
 
-__device__ __forceinline__ void bload16(f32x4& dst, int voff, i32x4 rsrc, int soff) {
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// the loads above are invisible to the compiler's wait-count pass: the kernel waits itself (vmcnt(0)) and then re-defines
+// bload16's loads are invisible to the compiler's wait-count pass: the kernel waits itself (vmcnt(0)) and then re-defines
 // the registers, so that every use is ordered behind the wait
 __device__ __forceinline__ void bpin(f32x4 (&b)[8]) {
     asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]));
@@ -511,16 +483,6 @@ __device__ __forceinline__ void bpin(f32x4 (&b)[8]) {
 // (a post-RA peephole written for the bf16 matrix pipe, where VALU instructions run beside the matrix unit).  The fp32 matrix
 // instructions run ON the vector ALU and a lone wave issues one instruction per ~5 cycles: a packed add costs the matrix stream
 // what a scalar one costs (tools/microbench/valu_cost.hip: 5.4 against 5.3 cycles), i.e. half per channel.
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 d;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {          // a * b + c
     f32x2 d;
     asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
@@ -832,7 +794,7 @@ __global__ __launch_bounds__(PN) void conv3d_wino_p_kernel(
         ci_n0 = __builtin_amdgcn_readfirstlane(e[1]) * 32;
     }
     load_b(B12, 1, 2, 0, ci_n0);
-    dma_wait();
+    vm_wait<0>();
     __syncthreads();
     bpin(B12);
 #pragma unroll
@@ -872,7 +834,10 @@ __global__ __launch_bounds__(PN) void conv3d_wino_p_kernel(
     int g = 0;                                              // chunk of the stream
     for (int it = 0; it < my_items; ++it) {
         const i32x4 ce = tab[2 * it];
-        const int brick = __builtin_amdgcn_readfirstlane(ce[0]), b = __builtin_amdgcn_readfirstlane(ce[2]);
+#if P_ABL & 8
+        const int brick = __builtin_amdgcn_readfirstlane(ce[0]);
+#endif
+        const int b = __builtin_amdgcn_readfirstlane(ce[2]);
         const int cpk = __builtin_amdgcn_readfirstlane(ce[3]);
         const int d0 = (cpk & 1023) * BD, h0 = ((cpk >> 10) & 1023) * BH, w0 = (cpk >> 20) * BW;
         const int n0 = ci_n0;
@@ -888,7 +853,7 @@ __global__ __launch_bounds__(PN) void conv3d_wino_p_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);
             TRQ(1 + 4 * (c & 3));
-            dma_wait();
+            vm_wait<0>();
             __syncthreads();                                // every wave is done with the halo of chunk g; chunk g + 1's has landed
             TRQ(2 + 4 * (c & 3));
             bpin(B03);
@@ -912,7 +877,7 @@ __global__ __launch_bounds__(PN) void conv3d_wino_p_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);
             TRQ(3 + 4 * (c & 3));
-            dma_wait();
+            vm_wait<0>();
             TRQ(4 + 4 * (c & 3));
             bpin(B12);
             ++g;
@@ -1184,7 +1149,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_wino_wgrad_kernel(
 
     if (st0 < st1) {
         stage(st0);
-        dma_wait();
+        vm_wait<0>();
         __syncthreads();
     }
     for (int st = st0; st < st1; ++st) {
@@ -1231,7 +1196,7 @@ __global__ __launch_bounds__(NTHR) void conv3d_wino_wgrad_kernel(
                 acc[phl * 4 + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ap[3], b3, acc[phl * 4 + 3], 0, 0, 0);
             }
         }
-        dma_wait();
+        vm_wait<0>();
         __syncthreads();                            // the next stage is in LDS; every wave is done with this one
     }
 
@@ -1513,7 +1478,7 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
         stage_first(st0);
         stage_issue(0);
         if (st0 + 1 < st1) { stage_next(); stage_issue(1); }
-        dma_wait();
+        vm_wait<0>();
         __syncthreads();
 #pragma unroll
         for (int g = 0; g < 3; ++g) T1(0, std::integral_constant<int, 0>{}, g);
@@ -1533,7 +1498,7 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (STEP == 3) {                        // the last read of this stage's buffer is done
-                    dma_wait();
+                    vm_wait<0>();
                     __syncthreads();                    // every wave is done with stage st; stage st + 1 has landed
                     if (st + 2 < st1) { stage_next(); stage_setup(par); stage_part(0); pend = true; }
                 }
@@ -1734,12 +1699,11 @@ __device__ __forceinline__ void wino_pack_one(const float* __restrict__ w, float
                 const float v = (float)G(t2[p][q][0], t2[p][q][1], t2[p][q][2], r);
                 // the same number as three bf16 parts (exact: 8 + 8 + 8 significand bits) for conv3d_winox.hip, behind the fp32 tensor:
                 //   [p][K / 16][part h, m, l][K half 2][N][8] bf16,  K index 16 c + 8 s + 4 half + e  ->  element s * 4 + e of its half
-                const unsigned uv = __builtin_bit_cast(unsigned, v);
-                const float r1 = v - __builtin_bit_cast(float, uv & 0xFFFF0000u);
-                const unsigned ur1 = __builtin_bit_cast(unsigned, r1);
-                const float r2 = r1 - __builtin_bit_cast(float, ur1 & 0xFFFF0000u);
-                const unsigned short part[3] = {(unsigned short)(uv >> 16), (unsigned short)(ur1 >> 16),
-                                                (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16)};
+                float ph, pm, pl;
+                split3_trunc(v, ph, pm, pl);
+                const unsigned short part[3] = {(unsigned short)(__builtin_bit_cast(unsigned, ph) >> 16),
+                                                (unsigned short)(__builtin_bit_cast(unsigned, pm) >> 16),
+                                                (unsigned short)(__builtin_bit_cast(unsigned, pl) >> 16)};
                 if (fwd != nullptr) {
                     const int pos = (p * 4 + q) * 4 + r;
                     fwd[((((size_t)pos * (cin / 8) + ci / 8) * 2 + (ci >> 2 & 1)) * cout + co) * 4 + (ci & 3)] = v;

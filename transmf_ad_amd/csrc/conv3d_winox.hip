@@ -32,7 +32,7 @@
 //
 // Replaces aten::conv3d / the data-gradient half of convolution_backward at /root/reference/models/networks.py:28,31,37,40,46.
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 #ifndef X_PF                // weights requested this many positions ahead (1 | 2)
 #define X_PF 2
@@ -51,8 +51,6 @@
 #endif
 
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef TMF_WINOX_TRACE
 // instrumented build (tools/winox_trace.py): shader-clock stamps of the phases of the SECOND item of workgroup 77, every wave.  The
@@ -89,30 +87,7 @@ constexpr int TAB = 256;                              // item table entries per 
 constexpr size_t X_LDS_BYTES = (size_t)TAB_OFF + 256 * 32;
 static_assert(EX_OFF + EX_BYTES >= 4 * RAWB && X_LDS_BYTES <= 160 * 1024, "LDS carving");
 
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)p;
-    return i32x4{(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// LDS-DMA of 16 bytes per lane: LDS byte = lds_wave_base + 16 * lane <- base + voff + soff; a lane outside the range delivers zeros
-__device__ __forceinline__ void blds16(int voff, i32x4 rsrc, int soff, unsigned lds_wave_base) {
-    asm volatile("" : "+s"(soff));                  // (a register, not a literal the instruction cannot encode)
-    rsrc = i32x4{__builtin_amdgcn_readfirstlane(rsrc[0]), __builtin_amdgcn_readfirstlane(rsrc[1]), __builtin_amdgcn_readfirstlane(rsrc[2]),
-                 __builtin_amdgcn_readfirstlane(rsrc[3])};  // (folds away where the descriptor already sits in scalar registers)
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rsrc), "s"(soff), "s"(lds_wave_base) : "memory");
-}
-// 16 bytes per lane to registers, invisible to the compiler's wait-count pass (the kernel counts its waits itself)
-__device__ __forceinline__ void bload16(i32x4& dst, int voff, i32x4 rsrc, int soff) {
-    asm volatile("" : "+s"(soff));
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void pin3(i32x4& a, i32x4& b, i32x4& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
-// a wide store reads its data registers after it has issued (conv3d_wino.hip: store_guard)
-__device__ __forceinline__ void store_guard() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 0");
-    __builtin_amdgcn_sched_barrier(0);
-}
 // workgroup barrier that leaves the weight loads in flight (the LDS traffic of this wave has been consumed by then)
 __device__ __forceinline__ void wg_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -125,6 +100,7 @@ __device__ __forceinline__ void wg_barrier_if(int flag) {
 }
 
 // exact 3-way bf16 split of 8 fp32 values (K order: y0[0..3], y1[0..3]); element 2 j in the low half of register j
+// (restates split3_trunc of tmf_device.h on a pair of values: through the call the kernels' instructions come out in another order)
 __device__ __forceinline__ void split8(const float (&y0)[4], const float (&y1)[4], i32x4& H, i32x4& M, i32x4& L) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -249,8 +225,8 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
         const unsigned base = lds0 + pr * 2 * RAWB + wave * 1024 + part * 8192;
         const int ho = plan[(6 + part) * XN];
         if (!(X_ABL & 4)) {
-            blds16(ho, xr, dm_c * (XCK * 4), base);
-            blds16(ho, xr, dm_c * (XCK * 4) + 32, base + RAWB);
+            blds16_uniform(ho, xr, dm_c * (XCK * 4), base);
+            blds16_uniform(ho, xr, dm_c * (XCK * 4) + 32, base + RAWB);
         }
         if (part == XDMA - 1) {
             if (++dm_c == nchunk) {
@@ -272,9 +248,9 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
     auto load_b = [&](int slot, int q8, int c, int n0) {
         if (X_ABL & 2) return;
         const int so = p_first + ((q8 >> 2) * q_hi + (q8 & 3)) * pos_b + c * chunk_b + n0 * 16;
-        bload16(Bq[slot][0], b_lane, ur, so);
-        bload16(Bq[slot][1], b_lane, ur, so + part_b);
-        bload16(Bq[slot][2], b_lane, ur, so + 2 * part_b);
+        bload16_pinned(Bq[slot][0], b_lane, ur, so);
+        bload16_pinned(Bq[slot][1], b_lane, ur, so + part_b);
+        bload16_pinned(Bq[slot][2], b_lane, ur, so + 2 * part_b);
     };
 
     // ---- input transform of this wave: planes da, db (d row pd of B^T), the h rows of its two ph, all four w columns ----

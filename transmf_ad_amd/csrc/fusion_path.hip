@@ -38,10 +38,6 @@ int tmf_xf_launch_colsum(int n_inst, const float* const* part, float* const* sma
 
 namespace {
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-#define TMF_TRY(call) do { int rc__ = (call); if (rc__ != TMF_OK) return rc__; } while (0)
-
 int check_desc(const char* fn, const tmf_fusion_desc* d) {
     TMF_REQUIRE_PTR(d);
     TMF_REQUIRE(d->B > 0 && d->N > 0 && d->depth >= 0 && d->depth <= TMF_FUSION_MAX_DEPTH, TMF_E_SHAPE,

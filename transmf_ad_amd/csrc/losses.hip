@@ -23,11 +23,9 @@
 //
 // Replaces the reference's op sequences at models/losses.py:122-128 (FALoss.forward) and :59-100 (SupConLoss.forward)
 // and their autograd backward.
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
-
-__device__ __forceinline__ int frag_row(int r, int hsel) { return (r & 3) + 8 * (r >> 2) + 4 * hsel; }
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll

@@ -19,8 +19,6 @@ namespace {
 
 constexpr int NL = TMF_SNET_BLOCKS;
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct LayerPlan {
     int cin, cout, k, pool;
     int D, H, W;            // conv input = conv output dims of the block
@@ -149,8 +147,6 @@ inline Vecs vecs_of(char* base, const LayerPlan& L) {
     float* v = (float*)(base + L.off_vec);
     return Vecs{v, v + L.cpad, v + 2 * L.cpad, v + 3 * L.cpad};
 }
-
-#define TMF_TRY(call) do { int rc__ = (call); if (rc__ != TMF_OK) return rc__; } while (0)
 
 }  // namespace
 

@@ -19,12 +19,11 @@
 // needs a whole row per workgroup, so there the tile IS the row: 64, 128 or 256 columns for dim 64, 128, 256.
 // Weight gradients stay plain GEMMs (dy^T . saved activations).
 #include <type_traits>
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
 constexpr int TM = 16, TTHR = 256;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct TokArgs {
     const float* A; const float* W; float* Y;
@@ -41,15 +40,6 @@ struct TokArgs {
     // Dropout epilogues (the *_MASK instances only): keep-mask [R][N], already scaled by 1 / (1 - p); masked copy of Y
     const float* mask; float* Y2;
 };
-
-__device__ __forceinline__ float gelu_f(float h) { return 0.5f * h * (1.f + erff(h * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float h) {
-    return 0.5f * (1.f + erff(h * 0.70710678118654752f)) + h * 0.3989422804014327f * expf(-0.5f * h * h);
-}
-__device__ __forceinline__ float half_sum(float v) {         // sum over the 32 lanes of a half-wave
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 8); v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
-    return v;
-}
 
 // LayerNorm prologue on one lane's chunk of a row (f32x4 or f32x2)
 __device__ __forceinline__ float hsum(f32x4 v) { return v[0] + v[1] + v[2] + v[3]; }

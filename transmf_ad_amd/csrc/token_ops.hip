@@ -6,7 +6,7 @@
 // reduces them once per workgroup.
 // Replaces F.layer_norm at /root/reference/models/networks.py:117,219 and
 // AdaptiveAvgPool1d/AdaptiveMaxPool1d + cat at :264-269, 276-281.
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 static thread_local char g_err[512] = "";
 
@@ -248,7 +248,6 @@ __global__ __launch_bounds__(256) void pack_conv_weights_bf16_kernel(const float
 // The fp32x mode's weight layouts (conv3d_fwd_split_kernel: every fp32 number as hi + mid + lo, three bf16 numbers, EXACT):
 //   fwd3  [p][t][co][ci]     = part p of w[co][ci][t]     dgrad3[p][T-1-t][ci][co] = part p of w[co][ci][t]
 // (what the host side did with permute / flip / three casts / two subtractions / stack: ~8 launches per layer and pass).
-__device__ __forceinline__ unsigned short tmf_bf16_bits(float a) { return __builtin_bit_cast(unsigned short, (__bf16)a); }
 __global__ __launch_bounds__(256) void pack_conv_weights_split3_kernel(const float* __restrict__ w, unsigned short* __restrict__ fwd,
                                                                        unsigned short* __restrict__ dgrad, int cout, int cin, int T) {
     const long n = (long)cout * cin * T;
@@ -265,11 +264,9 @@ __global__ __launch_bounds__(256) void pack_conv_weights_split3_kernel(const flo
         a = w[((long)co * cin + ci) * T + (T - 1 - tr)];
         dst = dgrad;
     }
-    const unsigned short h = tmf_bf16_bits(a);
-    const float r1 = a - __builtin_bit_cast(float, (unsigned)h << 16);           // exact
-    const unsigned short m = tmf_bf16_bits(r1);
-    const float r2 = r1 - __builtin_bit_cast(float, (unsigned)m << 16);          // exact, fits bf16
-    dst[e] = h; dst[n + e] = m; dst[2 * n + e] = tmf_bf16_bits(r2);
+    unsigned short h, m, l;
+    split3_rne(a, h, m, l);
+    dst[e] = h; dst[n + e] = m; dst[2 * n + e] = l;
 }
 
 // [B][R][C] <-> [B][C][R] through a 32 x 33 LDS tile (both sides coalesced); R = D*H*W voxels, C channels

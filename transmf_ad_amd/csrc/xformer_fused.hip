@@ -47,7 +47,7 @@
 // Dropout (options/option.py:39 `--dropout`; networks.py:131,133,153): the three keep-masks of an instance (after to_out,
 // after GELU, after the second Linear), already scaled by 1 / (1 - p), are INPUTS (NULL = inactive) — the random draw
 // stays with the caller, as in heads.hip.
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
@@ -58,8 +58,6 @@ constexpr int XDH = 32;            // dim_head
 constexpr int XP = XD + 4;         // LDS row pitch (floats) of a 128-wide tile
 constexpr int XTHR = 256;
 constexpr float XLOG2E = 1.4426950408889634f;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // phase time stamps of every wave (shader clock) for tools/xf_trace.py: only in builds with -DTMF_XF_TRACE
 // (TMF_EXTRA_FLAGS=-DTMF_XF_TRACE python -m transmf_ad_amd.build); the product kernels carry none of it
@@ -72,15 +70,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #else
 #define XF_STAMP(k) do { } while (0)
 #endif
-
-__device__ __forceinline__ float xgelu(float h) { return 0.5f * h * (1.f + erff(h * 0.70710678118654752f)); }
-__device__ __forceinline__ float xgelu_grad(float h) {
-    return 0.5f * (1.f + erff(h * 0.70710678118654752f)) + h * 0.3989422804014327f * expf(-0.5f * h * h);
-}
-__device__ __forceinline__ float xhalf_sum(float v) {        // sum over the 32 lanes of a half-wave
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 8); v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
-    return v;
-}
 
 // Columns of a lane's accumulator tiles: groups of G = min(TPW, 4) interleaved tiles, 16 G columns per group.
 template <int TPW> struct TileMap {
@@ -255,9 +244,9 @@ constexpr int XGP = XMLP + 4;
 // LayerNorm of a 128-wide row held as 4 values per lane of a half-wave (lane li owns columns 4 li .. 4 li + 3)
 __device__ __forceinline__ f32x4 ln_row(const f32x4 v, const float* __restrict__ g, const float* __restrict__ b, float eps,
                                         int li, float& mu, float& rs) {
-    mu = xhalf_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / 128.f);
+    mu = half_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / 128.f);
     const f32x4 d = {v[0] - mu, v[1] - mu, v[2] - mu, v[3] - mu};
-    const float var = xhalf_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 128.f);
+    const float var = half_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 128.f);
     rs = 1.f / sqrtf(var + eps);
     const f32x4 gg = ld4(g + li * 4), bb = ld4(b + li * 4);
     return f32x4{d[0] * rs * gg[0] + bb[0], d[1] * rs * gg[1] + bb[1], d[2] * rs * gg[2] + bb[2], d[3] * rs * gg[3] + bb[3]};
@@ -610,7 +599,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                     const bool ok = row < nv;
                     const f32x4 hv = {acc[gq * 4 + 0][r] + b1[0], acc[gq * 4 + 1][r] + b1[1], acc[gq * 4 + 2][r] + b1[2],
                                       acc[gq * 4 + 3][r] + b1[3]};
-                    f32x4 gv = {xgelu(hv[0]), xgelu(hv[1]), xgelu(hv[2]), xgelu(hv[3])};
+                    f32x4 gv = {gelu_f(hv[0]), gelu_f(hv[1]), gelu_f(hv[2]), gelu_f(hv[3])};
                     if (p.mask_g != nullptr && ok) {
                         const f32x4 mk = ld4(p.mask_g + (row0 + row) * XMLP + c0);
                         gv[0] *= mk[0]; gv[1] *= mk[1]; gv[2] *= mk[2]; gv[3] *= mk[3];
@@ -794,8 +783,8 @@ __global__ __launch_bounds__(XTHR, 1) void xf_bwd_q_kernel(const XfBwdQArgs p) {
         f32x4 xh, gg;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { xh[c] = (xv[c] - mu) * rs; gg[c] = dyv[c] * gam[c]; }
-        const float s1 = xhalf_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
-        const float s2 = xhalf_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
+        const float s1 = half_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
+        const float s2 = half_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
         f32x4 d, dm, px;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { d[c] = rs * (gg[c] - s1 - xh[c] * s2); px[c] = dyv[c] * xh[c]; }
@@ -836,7 +825,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_bwd_q_kernel(const XfBwdQArgs p) {
                 if (ok) {
                     const f32x4 hv = h_r[gq][r];
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) dv[c] = acc[gq * 4 + c][r] * xgelu_grad(hv[c]);
+                    for (int c = 0; c < 4; ++c) dv[c] = acc[gq * 4 + c][r] * gelu_grad_f(hv[c]);
                     if (p.mask_g != nullptr) {
                         const f32x4 mk = ld4(p.mask_g + (row0 + row) * XMLP + c0);
 #pragma unroll
@@ -880,8 +869,8 @@ __global__ __launch_bounds__(XTHR, 1) void xf_bwd_q_kernel(const XfBwdQArgs p) {
         f32x4 xh, gg;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { xh[c] = (xv[c] - mu) * rs; gg[c] = dfv[c] * gam[c]; }
-        const float s1 = xhalf_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
-        const float s2 = xhalf_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
+        const float s1 = half_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
+        const float s2 = half_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
         f32x4 d, dm, px;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { d[c] = rs * (gg[c] - s1 - xh[c] * s2) + r2v[c]; px[c] = dfv[c] * xh[c]; }
@@ -1065,8 +1054,8 @@ __global__ __launch_bounds__(XTHR, 1) void xf_bwd_q_kernel(const XfBwdQArgs p) {
         f32x4 xh, gg;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { xh[c] = (xv[c] - mu) * rs; gg[c] = dav[c] * gam[c]; }
-        const float s1 = xhalf_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
-        const float s2 = xhalf_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
+        const float s1 = half_sum(gg[0] + gg[1] + gg[2] + gg[3]) * (1.f / 128.f);
+        const float s2 = half_sum(gg[0] * xh[0] + gg[1] * xh[1] + gg[2] * xh[2] + gg[3] * xh[3]) * (1.f / 128.f);
         f32x4 d, px;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { d[c] = rs * (gg[c] - s1 - xh[c] * s2) + r1v[c] + ryv[c]; px[c] = dav[c] * xh[c]; }
