@@ -64,6 +64,9 @@ const char* tmf_last_error_string(void);
  *  c1_gram      <=0 -> 0, >=2 -> 2, 1    TMF_C1_GRAM: the same         1        yes       first block through its tap Gram matrix;
  *                                                                                         2 in the bf16 mode as well (tmf_c1_gram_bytes)
  *  c1_split     any, non-zero -> 1       TMF_C1_SPLIT: 0, else 1       1        yes       first block's z as exact bf16 splits (tmf_c1_split_mode)
+ *  pool_recompute 0..3                   TMF_POOL_RECOMPUTE: 0..3,     0        yes       max-pool routing of the whole-encoder fp32 train path:
+ *                                        else 0                                           0 kept by the forward, 1 recomputed in backward,
+ *                                                                                         2 / 3 recomputed in block 0 / in blocks 2, 4 only
  *  wino_cus     >= 0; 0: the environment TMF_WINO_CUS                  0        no        n > 0 caps the persistent Winograd workgroups at
  *                                                                                         min(n, compute units); 0 the device's count
  *  conv_rt      0..2                     TMF_CONV_RT: 1, 2, else 0     0        no*       register-tiled fp32 forward / data-gradient
@@ -254,6 +257,16 @@ int    tmf_c1_bwd_fused_bf16(const float* x, const float* w, const float* scale,
                              int pooled_bf16, int dw_layout, void* stream);
 int    tmf_c1_bn_pool_fwd(const float* x, const float* w, const float* scale, const float* shift, float* pooled,
                           int B, int D, int H, int W, int C, float slope, void* stream);
+/* The pool routing kept by the forward (fp32): tmf_c1_bn_pool_fwd_route also writes, per pooled window and channel, z_sel = the
+ * conv output of the window's FIRST maximum of scale*z + shift (torch scan order) and arg = its index 4 d + 2 h + w — both
+ * [b][D/2][H/2][W/2][C], float and byte; `pooled` is bit-identical to tmf_c1_bn_pool_fwd's.  tmf_c1_bwd_fused_route is
+ * tmf_c1_bwd_fused reading them instead of evaluating z (x still feeds D): same workspace, bit-identical dw, dgamma, dbeta. */
+int    tmf_c1_bn_pool_fwd_route(const float* x, const float* w, const float* scale, const float* shift, float* pooled,
+                                float* z_sel, unsigned char* arg, int B, int D, int H, int W, int C, float slope, void* stream);
+int    tmf_c1_bwd_fused_route(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, const float* dpool, const float* z_sel, const unsigned char* arg,
+                              const void* gram, float* dw, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                              int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream);
 int    tmf_c1_bwd_reduce(const float* x, const float* w, const float* scale, const float* shift,
                          const float* mean, const float* invstd, const float* dpool, float* partial,
                          int B, int D, int H, int W, int C, float slope, void* stream);
@@ -326,6 +339,16 @@ int tmf_bn_act_pool_bwd_reduce_t(const void* z, const void* dout, const float* s
 int tmf_bn_act_pool_bwd_apply_t(const void* z, const void* dout, const float* scale, const float* shift,
                                 const float* mean, const float* invstd, const float* coef, void* dz,
                                 int B, int D, int H, int W, int C, int pool, float slope, int io, void* stream);
+
+/* Max pool, all float, with the routing kept: tmf_bn_act_pool_fwd_route is tmf_bn_act_pool_fwd(.., TMF_POOL_MAX2, ..) that also
+ * writes z_sel [b][D/2][H/2][W/2][C], the z of each window's first maximum of z*scale + shift (`out` bit-identical);
+ * tmf_bn_act_pool_bwd_reduce_route reads (z_sel, dout) instead of (z, dout) — a ninth of the bytes — and writes the partials of
+ * tmf_bn_act_pool_bwd_reduce bit for bit (same tmf_bn_act_pool_bwd_blocks).  The apply pass still needs z. */
+int tmf_bn_act_pool_fwd_route(const float* z, const float* scale, const float* shift, float* out, float* z_sel,
+                              int B, int D, int H, int W, int C, float slope, void* stream);
+int tmf_bn_act_pool_bwd_reduce_route(const float* z_sel, const float* dout, const float* scale, const float* shift,
+                                     const float* mean, const float* invstd, float* partial,
+                                     int B, int D, int H, int W, int C, float slope, void* stream);
 
 /* Sum `nblk` partial rows of `ncol` floats (fp64 accumulation) into out[ncol]. */
 int tmf_colsum_finalize(const float* partial, int nblk, int ncol, float* out, void* stream);
@@ -531,6 +554,11 @@ int    tmf_scale_flip(const float* src, float* dst, const float* minmax, const u
 #define TMF_SNET_ALGO_C1_GRAM  0x2000             /* c1_gram: the first block through the tap Gram matrix of its input */
 #define TMF_SNET_ALGO_C1_GRAM_BF16 0x4000         /* c1_gram 2: in the bf16 mode as well (off by default: slower there) */
 #define TMF_SNET_ALGO_C1_SPLIT 0x8000             /* c1_split: z of the first block (fp32) as exact 3-way bf16 splits on the bf16 pipe */
+/* pool_recompute: the fp32 train passes RECOMPUTE the max-pool routing in backward instead of reading what the forward kept in
+ * `saved` (z of each window's maximum, + its index in block 0) — in the first block / in the pooled BatchNorm blocks (2, 4).
+ * Both clear by default: the routing is kept (tmf_snet_saved_bytes counts it); results are bit-identical either way. */
+#define TMF_SNET_ALGO_POOL_REC_C1 0x10000
+#define TMF_SNET_ALGO_POOL_REC_BN 0x20000
 int  tmf_snet_algo_flags(void);
 int  tmf_c1_split_mode(void);                     /* the option "c1_split" (tmf_set_option) */
 typedef struct tmf_snet_desc {

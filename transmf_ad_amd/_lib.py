@@ -75,6 +75,8 @@ PROTOTYPES = {
     "tmf_c1_stats_g_bf16": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
     "tmf_c1_bwd_fused_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "tmf_c1_bn_pool_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "tmf_c1_bn_pool_fwd_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "tmf_c1_bwd_fused_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),
     "tmf_c1_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "tmf_c1_stats_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "tmf_c1_bn_pool_fwd_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
@@ -84,6 +86,8 @@ PROTOTYPES = {
     "tmf_conv3d_wgrad_bf16_t": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "tmf_bn_act_pool_fwd_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "tmf_bn_act_pool_bwd_reduce_t": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "tmf_bn_act_pool_fwd_route": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "tmf_bn_act_pool_bwd_reduce_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "tmf_bn_act_pool_bwd_apply_t": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "tmf_c1_bwd_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "tmf_c1_bwd_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),

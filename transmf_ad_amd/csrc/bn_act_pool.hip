@@ -7,6 +7,9 @@
 // scale/shift, and ONE fused pass here does normalise + LeakyReLU + pool.  Backward mirrors
 // it: one pass reduces sum(dy), sum(dy*xhat) straight from (z, dout) — the pool routing and
 // the LeakyReLU mask are recomputed, never stored — and one pass writes dz.
+// Max pool, fp32 (the whole-encoder path, snet_path.hip): the forward can also keep z_sel, the z of each window's
+// routed voxel (ROUTE forms below); the reduce pass then reads (z_sel, dout), a ninth of the bytes, and leaves the
+// same partials bit for bit.
 //
 // Thread mapping (all kernels): a workgroup is a [ROWS][CQ] grid, CQ = C/VEC channel groups;
 // a thread keeps its channel group for the whole launch (so per-channel partials live in
@@ -61,10 +64,13 @@ __host__ __device__ inline Geo make_geo(int B, int D, int H, int W, int C, int p
 // ---------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------
-template <int VEC, int POOL, typename ZT = float, typename YT = float>
+// ROUTE (max pool, float z): also writes z_sel[o] = the z of the FIRST maximum of y = z*scale + shift in the window
+// (the strict '>' scan of bn_bwd_reduce_kernel — not of the activation, which `out` is the maximum of as before)
+template <int VEC, int POOL, typename ZT = float, typename YT = float, bool ROUTE = false>
 __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(
     const ZT* __restrict__ z, const float* __restrict__ scale, const float* __restrict__ shift,
-    YT* __restrict__ out, Geo g, int CQ, int ROWS, float slope) {
+    YT* __restrict__ out, Geo g, int CQ, int ROWS, float slope, float* __restrict__ z_sel = nullptr) {
+    static_assert(!ROUTE || (POOL == TMF_POOL_MAX2 && std::is_same<ZT, float>::value), "ROUTE: max pool over a float z");
     typedef typename Vec<VEC>::T V;
     const int cq = threadIdx.x % CQ, prow = threadIdx.x / CQ;
     if (prow >= ROWS) return;
@@ -89,6 +95,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(
         } else {
 #pragma unroll
             for (int q = 0; q < VEC; ++q) res[q] = POOL == TMF_POOL_MAX2 ? -INFINITY : 0.f;
+            V ymax, zs;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int dd = 2 * od + (k >> 2), hh = 2 * oh + ((k >> 1) & 1), ww = 2 * ow + (k & 1);
@@ -99,8 +106,14 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(
                     const float a = y > 0.f ? y : y * slope;
                     if (POOL == TMF_POOL_MAX2) res[q] = fmaxf(res[q], a);
                     else res[q] += a;
+                    if (ROUTE) {
+                        const bool up = k == 0 || y > ymax[q];
+                        ymax[q] = up ? y : ymax[q];
+                        zs[q] = up ? v[q] : zs[q];
+                    }
                 }
             }
+            if (ROUTE) stv<VEC>(z_sel + o * g.C + c, zs);
             if (POOL == TMF_POOL_AVG2) {
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) res[q] *= 0.125f;
@@ -190,7 +203,8 @@ struct Window {
     }
 };
 
-template <int VEC, int POOL, typename ZT = float, typename YT = float>
+// ROUTE (max pool): `z` is the forward's z_sel (pooled shape) — one read per window instead of eight, the same sums
+template <int VEC, int POOL, typename ZT = float, typename YT = float, bool ROUTE = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     const ZT* __restrict__ z, const YT* __restrict__ dout, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -217,10 +231,16 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
             const int wd0 = t % g.WD;
             const int b = t / g.WD;
             if (!(wd0 < OD && wh0 < OH && ww0 < OW)) continue;
-            const V go = ldv<VEC>(dout + ((((long)b * OD + wd0) * OH + wh0) * OW + ww0) * g.C + c);
+            const long po = ((((long)b * OD + wd0) * OH + wh0) * OW + ww0) * g.C + c;
+            const V go = ldv<VEC>(dout + po);
             V ymax, zs;
+            if (ROUTE) {
+                zs = ldv<VEC>(z + po);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
+                for (int q = 0; q < VEC; ++q) ymax[q] = zs[q] * sc[q] + sh[q];     // the y the scan below would have kept
+            }
+#pragma unroll
+            for (int k = 0; k < (ROUTE ? 0 : 8); ++k) {
                 const int dd = 2 * wd0 + (k >> 2), hh = 2 * wh0 + ((k >> 1) & 1), ww = 2 * ww0 + (k & 1);
                 const V v = ldv<VEC>(z + (((long)(b * g.D + dd) * g.H + hh) * g.W + ww) * g.C + c);
 #pragma unroll
@@ -532,6 +552,26 @@ extern "C" int tmf_bn_act_pool_fwd(const float* z, const float* scale, const flo
     return tmf_bn_act_pool_fwd_t(z, scale, shift, out, B, D, H, W, C, pool, slope, 0, stream);
 }
 
+// max pool, all float, with the routing output z_sel [B][D/2][H/2][W/2][C] (the same launch shape as the plain form)
+extern "C" int tmf_bn_act_pool_fwd_route(const float* z, const float* scale, const float* shift, float* out, float* z_sel,
+                                         int B, int D, int H, int W, int C, float slope, void* stream) {
+    TMF_REQUIRE_PTR(z); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift); TMF_REQUIRE_PTR(out); TMF_REQUIRE_PTR(z_sel);
+    int rc = check_geo("tmf_bn_act_pool_fwd_route", B, D, H, W, C, TMF_POOL_MAX2);
+    if (rc) return rc;
+    TMF_REQUIRE_ALIGNED(z); TMF_REQUIRE_ALIGNED(out); TMF_REQUIRE_ALIGNED(z_sel);
+    const Geo g = make_geo(B, D, H, W, C, TMF_POOL_MAX2);
+    const long nout = (long)B * (D / 2) * (H / 2) * (W / 2);
+    if (nout == 0) return TMF_OK;
+    const EwPlan p = plan_ew(nout, C);
+    if (p.vec == 4)
+        hipLaunchKernelGGL((bn_act_pool_fwd_kernel<4, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), 0, (hipStream_t)stream,
+                           z, scale, shift, out, g, p.cq, p.rows, slope, z_sel);
+    else
+        hipLaunchKernelGGL((bn_act_pool_fwd_kernel<1, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), 0, (hipStream_t)stream,
+                           z, scale, shift, out, g, p.cq, p.rows, slope, z_sel);
+    return tmf_launch_result("tmf_bn_act_pool_fwd_route");
+}
+
 extern "C" int tmf_bn_act_pool_bwd_blocks(int B, int D, int H, int W, int C, int pool) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
     const Geo g = make_geo(B, D, H, W, C, pool);
@@ -557,6 +597,27 @@ extern "C" int tmf_bn_act_pool_bwd_reduce_t(const void* z, const void* dout, con
 #undef L_RED
 #undef K_RED
     return tmf_launch_result("tmf_bn_act_pool_bwd_reduce");
+}
+
+// max pool, all float, from the forward's z_sel: the grid, the window -> thread map and the order of additions of the plain form
+extern "C" int tmf_bn_act_pool_bwd_reduce_route(const float* z_sel, const float* dout, const float* scale, const float* shift,
+                                                const float* mean, const float* invstd, float* partial,
+                                                int B, int D, int H, int W, int C, float slope, void* stream) {
+    TMF_REQUIRE_PTR(z_sel); TMF_REQUIRE_PTR(dout); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift);
+    TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(invstd); TMF_REQUIRE_PTR(partial);
+    int rc = check_geo("tmf_bn_act_pool_bwd_reduce_route", B, D, H, W, C, TMF_POOL_MAX2);
+    if (rc) return rc;
+    TMF_REQUIRE_ALIGNED(z_sel); TMF_REQUIRE_ALIGNED(dout);
+    const Geo g = make_geo(B, D, H, W, C, TMF_POOL_MAX2);
+    const EwPlan p = plan_ew(g.nwin, C);
+    const size_t lds = (size_t)p.rows * 2 * C * 4;
+    if (p.vec == 4)
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<4, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream,
+                           z_sel, dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope);
+    else
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<1, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream,
+                           z_sel, dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope);
+    return tmf_launch_result("tmf_bn_act_pool_bwd_reduce_route");
 }
 
 extern "C" int tmf_bn_act_pool_bwd_reduce(const float* z, const float* dout, const float* scale, const float* shift,

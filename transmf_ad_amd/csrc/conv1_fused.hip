@@ -44,6 +44,9 @@ enum { MODE_STATS = 0, MODE_FWD = 1, MODE_REDUCE = 2, MODE_WGRAD = 3, MODE_RD = 
 // MODE_RD (round 5): MODE_REDUCE plus D[tap][c] = sum_voxel x[voxel + tap] dy[voxel][c] — dy is ONE element per pooling window, so D is 27
 // reads and multiply-adds per window; with the tap Gram matrix of the forward (conv1_gram.hip) the weight gradient follows without
 // a second pass (tmf_c1_bwd_fused).
+// ROUTE (fp32): the forward also keeps, per pooled window and channel, zs = the z of the first maximum and arg = its index k, and
+// MODE_RD reads (dP, zs, arg) instead of evaluating z: no MFMAs, no bf16 images, only the fp32 halo D is formed from.  The lane ->
+// window map, the brick walk and the order of every addition are those of the recomputing pass, so its slabs are the same bit for bit.
 
 // bf16 passes: the halo brick lives in LDS as bf16, TWICE — copy c stores element e at index e + c — so that the pair
 // (x[w], x[w + 1]) is one aligned dword for every w (even w: copy 0, odd w: copy 1).  A lane then fetches two taps per
@@ -76,6 +79,8 @@ struct Args {
     const float* coef;     // [2][C] (WGRAD)
     const void* dpool;     // [B][D/2][H/2][W/2][C] (REDUCE, WGRAD); float, or bf16 when P16
     void* pooled;          // (FWD)
+    float* zsel;           // ROUTE: [B][D/2][H/2][W/2][C] z of each window's first maximum (FWD writes, RD reads)
+    unsigned char* parg;   // ROUTE: its index k = 4 d + 2 h + w in the window, same shape
     float* partial;        // STATS/REDUCE/RD: [nblk][2][C];  WGRAD: [nblk][27][C]
     float* partial2;       // RD: [nblk][27][C]
     int D, H, W, C;
@@ -99,9 +104,12 @@ __device__ __forceinline__ tmf_bf16x8 pack8(const float (&v)[8]) {
 // arithmetic), and — what counts as much — the bf16 MFMAs do not share the vector ALU's issue port, so the BatchNorm / pooling /
 // routing arithmetic of these passes runs beside them instead of in between.  The fp32 halo stays next to the images for the passes
 // that multiply the inputs themselves (D of MODE_RD, the tap-gradient product of MODE_WGRAD: fp32 as before).
-template <int MODE, bool BF16, bool P16 = false, bool SPLIT = false>     // P16: pooled / dpool are bf16 tensors (bf16 activation storage)
-__global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_kernel(Args a) {   // <= 256 registers: MFMA results in VGPRs (no v_accvgpr_read copies)
+template <int MODE, bool BF16, bool P16 = false, bool SPLIT = false, bool ROUTE = false>     // P16: pooled / dpool are bf16 tensors (bf16 activation storage)
+__global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT && ROUTE) ? 4 : 2) void conv1_fused_kernel(Args a) {   // <= 256 registers: MFMA results in VGPRs (no v_accvgpr_read copies)
     static_assert(!(BF16 && SPLIT), "SPLIT is the fp32 mode's variant");
+    static_assert(!ROUTE || (!BF16 && !P16 && (MODE == MODE_FWD || (MODE == MODE_RD && !SPLIT))),
+                  "ROUTE: the fp32 forward (either form of z) and the one-pass backward, which evaluates no z and so has one form");
+    constexpr bool NOZ = ROUTE && MODE == MODE_RD;           // the routing comes from the forward: no weights, no MFMAs
     constexpr bool B16L = BF16 || SPLIT;                    // bf16 halo image(s) in LDS
     constexpr int NIMG = SPLIT ? 3 : 1;
     constexpr bool KEEP32 = SPLIT && (MODE == MODE_RD || MODE == MODE_WGRAD);
@@ -140,7 +148,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
                 bwb[0][m] = pack8(v);
             }
         }
-    } else {
+    } else if (!NOZ) {
 #pragma unroll
         for (int s = 0; s < 14; ++s) {
             const int tap = 2 * s + hsel;
@@ -259,9 +267,18 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
         const bool full = cur.full_dh && w0 + TW <= a.W;
         cur = next_crd(cur);                 // from here on: the NEXT brick (prefetch target, and the next iteration's own)
         if (tile > tile_begin) __syncthreads();
+        // the routed SPLIT forward is three registers over its 128 (four waves per SIMD) with the image offsets hdst[] kept across
+        // bricks: it derives them per brick from a thread index the compiler cannot see through (a few instructions per brick)
+        constexpr bool REDST = SPLIT && ROUTE && MODE == MODE_FWD;
+        int tid_b = tid;
+        if (REDST) asm volatile("" : "+v"(tid_b));
 #pragma unroll
         for (int q = 0; q < HVN; ++q) {
             const int e = tid + q * 256;
+            if (REDST) {
+                const int eb = tid_b + q * 256;
+                hdst[q] = (eb / (HW * HH)) * BPLANE + ((eb / HW) % HH) * BROW + eb % HW;
+            }
             if (SPLIT) {
                 if (e < NHALO) {
                     float ph, pm, pl;
@@ -339,7 +356,7 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
 #pragma unroll
             for (int m = 0; m < 3; ++m) mma(ti, m, pr);
         };
-        if (!LAZY) {
+        if (!LAZY && !NOZ) {
             const int vox = (((i >> 3) & 1) * HH + 2 * ((i >> 2) & 1) + ((i >> 1) & 1)) * HW + 2 * ((i >> 4) & 1) + (i & 1);
             int a_vox[NTI];
 #pragma unroll
@@ -416,11 +433,32 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
             const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
                 reinterpret_cast<char*>(pbase) + (size_t)b * OD * OH * OW * a.C * PSZ, 0, OD * OH * OW * a.C * PSZ, 0x00020000);
             const int pv = (FULL || ohb + hsel < OH) ? pl_lane : OOB;      // this lane's voffset (out of range = no window)
+            // ROUTE: zs at the pooled tensor's own offsets, arg at a quarter of them (bytes; 2^31 / 4 is still out of range)
+            const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(
+                reinterpret_cast<char*>(a.zsel) + (ROUTE ? (size_t)b * OD * OH * OW * a.C * 4 : 0), 0, ROUTE ? OD * OH * OW * a.C * 4 : 0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(
+                a.parg + (ROUTE ? (size_t)b * OD * OH * OW * a.C : 0), 0, ROUTE ? OD * OH * OW * a.C : 0, 0x00020000);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int ow = owb + q;
                 const bool win_u = FULL || (od < OD && ow < OW);           // wave-uniform part of "the window exists"
                 const int psoff = ((od * OH + ohb) * OW + ow) * a.C * PSZ;
+                if (NOZ) {
+                    float g = 0.f, zs = 0.f;                                   // lanes without a window read zeros
+                    int arg = 0;
+                    if (win_u) {
+                        g = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr, pv, psoff, 0));
+                        zs = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(zr, pv, psoff, 0));
+                        arg = __builtin_amdgcn_raw_buffer_load_b8(ar, (int)((unsigned)pv >> 2), psoff / PSZ, 0) & 7;
+                    }
+                    const float gl = g * (zs * sc + sh > 0.f ? 1.f : a.slope);  // ymax of the recomputing form IS fma(zs, sc, sh)
+                    s1 += gl;
+                    s2 += gl * ((zs - mu) * is);
+                    const int vx = org + hsel * 2 * HW + ((arg >> 2) & 1) * HH * HW + ((arg >> 1) & 1) * HW + 2 * q + (arg & 1);
+#pragma unroll
+                    for (int t = 0; t < 27; ++t) dacc[t] = fmaf(halo[vx + tapoff(t)], gl, dacc[t]);
+                    continue;
+                }
                 float y[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) y[k] = z[8 * q + k] * sc + sh;
@@ -432,6 +470,18 @@ __global__ __launch_bounds__(256, MODE == 3 && !SPLIT ? 4 : 2) void conv1_fused_
                     if (win_u && !(TMF_C1X_ABL & 1)) {
                         if (P16) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(tmf_pack_bf16(best, 0.f) & 0xFFFFu), pr, pv, psoff, 0);
                         else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, best), pr, pv, psoff, 0);
+                        if (ROUTE) {                            // the routing MODE_RD derives: the FIRST k with y[k] == ymax
+                            float zs = z[8 * q + 7];
+                            int arg = 7;
+#pragma unroll
+                            for (int k = 6; k >= 0; --k) {
+                                const bool hit = y[k] == ymax;
+                                zs = hit ? z[8 * q + k] : zs;
+                                arg = hit ? k : arg;
+                            }
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, zs), zr, pv, psoff, 0);
+                            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)arg, ar, (int)((unsigned)pv >> 2), psoff / PSZ, 0);
+                        }
                     }
                     continue;
                 }
@@ -633,14 +683,20 @@ extern "C" int tmf_c1_stats_bf16(const float* x, const float* w, float* stat_par
 }
 
 static int c1_bn_pool_fwd(bool bf16, bool p16, const float* x, const float* w, const float* scale, const float* shift,
-                          void* pooled, int B, int D, int H, int W, int C, float slope, void* stream) {
+                          void* pooled, int B, int D, int H, int W, int C, float slope, void* stream,
+                          float* z_sel = nullptr, unsigned char* arg = nullptr) {
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift); TMF_REQUIRE_PTR(pooled);
     int rc = check("tmf_c1_bn_pool_fwd", B, D, H, W, C);
     if (rc) return rc;
     const Plan p = make_plan(B, D, H, W, C, tmf_opt(TMF_OPT_C1_FWD_MULT) * SLAB_BLOCKS);     // a few bricks per workgroup (halo prefetch)
     Args a = base_args(x, w, D, H, W, C, p, slope);
-    a.scale = scale; a.shift = shift; a.pooled = pooled;
+    a.scale = scale; a.shift = shift; a.pooled = pooled; a.zsel = z_sel; a.parg = arg;
     TMF_REQUIRE(bf16 || !p16, TMF_E_ARG, "tmf_c1_bn_pool_fwd: bf16 tensors only with the bf16 kernels");
+    if (z_sel != nullptr) {
+        if (c1_split_mode()) hipLaunchKernelGGL((conv1_fused_kernel<MODE_FWD, false, false, true, true>), dim3(p.nblk, p.nby), dim3(256), 0, (hipStream_t)stream, a);
+        else                 hipLaunchKernelGGL((conv1_fused_kernel<MODE_FWD, false, false, false, true>), dim3(p.nblk, p.nby), dim3(256), 0, (hipStream_t)stream, a);
+        return tmf_launch_result("tmf_c1_bn_pool_fwd_route");
+    }
     if (bf16 && p16) hipLaunchKernelGGL((conv1_fused_kernel<MODE_FWD, true, true>), dim3(p.nblk, p.nby), dim3(256), 0, (hipStream_t)stream, a);
     else if (bf16)   hipLaunchKernelGGL((conv1_fused_kernel<MODE_FWD, true>), dim3(p.nblk, p.nby), dim3(256), 0, (hipStream_t)stream, a);
     else if (c1_split_mode()) hipLaunchKernelGGL((conv1_fused_kernel<MODE_FWD, false, false, true>), dim3(p.nblk, p.nby), dim3(256), 0, (hipStream_t)stream, a);
@@ -650,6 +706,11 @@ static int c1_bn_pool_fwd(bool bf16, bool p16, const float* x, const float* w, c
 extern "C" int tmf_c1_bn_pool_fwd(const float* x, const float* w, const float* scale, const float* shift,
                                   float* pooled, int B, int D, int H, int W, int C, float slope, void* stream) {
     return c1_bn_pool_fwd(false, false, x, w, scale, shift, pooled, B, D, H, W, C, slope, stream);
+}
+extern "C" int tmf_c1_bn_pool_fwd_route(const float* x, const float* w, const float* scale, const float* shift, float* pooled,
+                                        float* z_sel, unsigned char* arg, int B, int D, int H, int W, int C, float slope, void* stream) {
+    TMF_REQUIRE_PTR(z_sel); TMF_REQUIRE_PTR(arg);
+    return c1_bn_pool_fwd(false, false, x, w, scale, shift, pooled, B, D, H, W, C, slope, stream, z_sel, arg);
 }
 extern "C" int tmf_c1_bn_pool_fwd_bf16(const float* x, const float* w, const float* scale, const float* shift,
                                        void* pooled, int B, int D, int H, int W, int C, float slope, int pooled_bf16,
@@ -749,7 +810,7 @@ extern "C" size_t tmf_c1_bwd_fused_workspace_bytes(int B, int D, int H, int W, i
 static int c1_bwd_fused(bool bf16, bool p16, const float* x, const float* w, const float* scale, const float* shift, const float* mean,
                         const float* invstd, const void* dpool, const void* gram, float* dw, float* dgamma, float* dbeta,
                         void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int C, float slope,
-                        int dw_layout, void* stream) {
+                        int dw_layout, void* stream, const float* z_sel = nullptr, const unsigned char* arg = nullptr) {
     TMF_REQUIRE(dw_layout == TMF_DW_TAPMAJOR || dw_layout == TMF_DW_REFERENCE, TMF_E_ARG, "tmf_c1_bwd_fused: unknown dw_layout %d", dw_layout);
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift); TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(invstd);
     TMF_REQUIRE_PTR(dpool); TMF_REQUIRE_PTR(gram); TMF_REQUIRE_PTR(dw); TMF_REQUIRE_PTR(workspace);
@@ -767,9 +828,11 @@ static int c1_bwd_fused(bool bf16, bool p16, const float* x, const float* w, con
     float* scratch = slabs + (size_t)p.nblk * n;
     float* dred = scratch + (size_t)tmf_reduce_groups(p.nblk) * n;
     a.partial = part; a.partial2 = slabs;
+    a.zsel = const_cast<float*>(z_sel); a.parg = const_cast<unsigned char*>(arg);       // (read only in MODE_RD)
     hipStream_t s = (hipStream_t)stream;
     TMF_REQUIRE(bf16 || !p16, TMF_E_ARG, "tmf_c1_bwd_fused: bf16 tensors only with the bf16 kernels");
-    if (bf16 && p16) hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, true, true>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
+    if (z_sel != nullptr) hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, false, false, false, true>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
+    else if (bf16 && p16) hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, true, true>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
     else if (bf16)   hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, true>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
     else if (c1_split_mode()) hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, false, false, true>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
     else             hipLaunchKernelGGL((conv1_fused_kernel<MODE_RD, false>), dim3(p.nblk, p.nby), dim3(256), 0, s, a);
@@ -784,6 +847,15 @@ extern "C" int tmf_c1_bwd_fused(const float* x, const float* w, const float* sca
                                 int dw_layout, void* stream) {
     return c1_bwd_fused(false, false, x, w, scale, shift, mean, invstd, dpool, gram, dw, dgamma, dbeta, workspace, workspace_bytes,
                         B, D, H, W, C, slope, dw_layout, stream);
+}
+// with the routing the forward kept (tmf_c1_bn_pool_fwd_route): the same slabs and results without evaluating z
+extern "C" int tmf_c1_bwd_fused_route(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                                      const float* invstd, const float* dpool, const float* z_sel, const unsigned char* arg,
+                                      const void* gram, float* dw, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                      int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream) {
+    TMF_REQUIRE_PTR(z_sel); TMF_REQUIRE_PTR(arg);
+    return c1_bwd_fused(false, false, x, w, scale, shift, mean, invstd, dpool, gram, dw, dgamma, dbeta, workspace, workspace_bytes,
+                        B, D, H, W, C, slope, dw_layout, stream, z_sel, arg);
 }
 // the bf16 mode's form (gram from tmf_c1_stats_g_bf16): z and D from the volume and the taps rounded to bf16, dy unrounded — the
 // weight gradient is that of the bf16 forward WITHOUT the second rounding of dz that tmf_c1_bwd_wgrad_bf16's product performs

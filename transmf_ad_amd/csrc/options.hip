@@ -36,6 +36,9 @@ constexpr Row kRows[] = {
     {TMF_OPT_C1_GRAM, "c1_gram", "TMF_C1_GRAM", 1, nullptr, nullptr, clamp02, clamp02,
      {TMF_SNET_ALGO_C1_GRAM, TMF_SNET_ALGO_C1_GRAM | TMF_SNET_ALGO_C1_GRAM_BF16}},
     {TMF_OPT_C1_SPLIT, "c1_split", "TMF_C1_SPLIT", 1, nullptr, nullptr, nonzero, nonzero, {TMF_SNET_ALGO_C1_SPLIT}},
+    {TMF_OPT_POOL_RECOMPUTE, "pool_recompute", "TMF_POOL_RECOMPUTE", 0, "0, 1, 2 or 3", [](int v) { return v >= 0 && v <= 3; }, nullptr,
+     [](int v) { return v >= 0 && v <= 3 ? v : 0; },
+     {TMF_SNET_ALGO_POOL_REC_C1 | TMF_SNET_ALGO_POOL_REC_BN, TMF_SNET_ALGO_POOL_REC_C1, TMF_SNET_ALGO_POOL_REC_BN}},
     {TMF_OPT_WINO_CUS, "wino_cus", "TMF_WINO_CUS", 0, ">= 0", [](int v) { return v >= 0; }, [](int v) { return v ? v : UNSET; },
      nullptr, {}},
     {TMF_OPT_CONV_RT, "conv_rt", "TMF_CONV_RT", 0, "0, 1 or 2", in02, nullptr, [](int v) { return v == 1 || v == 2 ? v : 0; }, {}},

@@ -28,6 +28,8 @@ struct LayerPlan {
     bool wgf, wgd, wgw;     // fp32: forward / data gradient / weight gradient in the Winograd form (tmf_set_option("conv_wino", ..), conv3d_wino.hip)
     bool x16, z16, o16;     // bf16 storage of the block input, the raw conv output (and dz), the block output
     size_t off_z, off_out, off_vec, off_wf, off_wd;     // in the saved workspace
+    bool route;             // max-pooled block, fp32: the forward keeps the pool routing for the backward (option "pool_recompute")
+    size_t off_zsel, off_arg;   // ... z of each window's first maximum (float, pooled shape); block 0: + its index (a byte)
     size_t x_bytes, z_bytes, out_bytes;
     int cpad;               // floats between the per-channel vectors (mean | invstd | scale | shift)
 };
@@ -53,8 +55,9 @@ int check_desc(const char* fn, const tmf_snet_desc* d) {
     return TMF_OK;
 }
 
-Plan make_plan(const tmf_snet_desc& d) {
+Plan make_plan(const tmf_snet_desc& d, bool train = true) {
     Plan p;
+    const int rec = tmf_opt(TMF_OPT_POOL_RECOMPUTE);        // 0 keep the routing, 1 recompute it, 2 / 3: in block 0 / blocks 2, 4 only
     const int q = d.dim / 4, h = d.dim / 2, dm = d.dim, d2 = d.dim * 2;
     const int cin[NL] = {1, q, q, h, h, dm, d2}, cout[NL] = {q, q, h, h, dm, d2, dm};
     const int ks[NL] = {3, 3, 3, 3, 3, 3, 1};
@@ -92,6 +95,11 @@ Plan make_plan(const tmf_snet_desc& d) {
         L.cpad = (int)(up256((size_t)L.cout * 4) / 4);
         L.off_z = off; off += up256(L.z_bytes);
         L.off_out = off; off += up256(L.out_bytes);
+        // fp32 train passes; block 0 only where its backward is the one pass over the volume (the Gram data: below)
+        L.route = train && d.precision == TMF_PREC_FP32 && L.pool == TMF_POOL_MAX2 && ovox > 0 &&
+                  (l == 0 ? rec != 1 && rec != 2 && tmf_c1_gram_bytes(d.B, L.D, L.H, L.W, L.cout) > 0 : rec != 1 && rec != 3);
+        L.off_zsel = off; off += L.route ? up256(ovox * L.cout * 4) : 0;
+        L.off_arg = off; off += L.route && l == 0 ? up256(ovox * L.cout) : 0;
         L.off_vec = off; off += (size_t)4 * L.cpad * 4;
         const size_t wn = (size_t)L.k * L.k * L.k * L.cin * L.cout;
         const size_t wino_b = tmf_conv3d_wino_weight_bytes(L.cin, L.cout);
@@ -242,8 +250,14 @@ extern "C" int tmf_snet_train_fwd(const tmf_snet_desc* d, const float* vol, cons
             if (l == 0) {
                 if (b16) TMF_TRY(tmf_c1_bn_pool_fwd_bf16(vol, (const float*)wf, v.scale, v.shift, o, d->B, L.D, L.H, L.W, L.cout,
                                                          d->slope[l], L.o16 ? 1 : 0, stream));
+                else if (L.route) TMF_TRY(tmf_c1_bn_pool_fwd_route(vol, (const float*)wf, v.scale, v.shift, (float*)o, (float*)(base + L.off_zsel),
+                                                                   (unsigned char*)(base + L.off_arg), d->B, L.D, L.H, L.W, L.cout, d->slope[l],
+                                                                   stream));
                 else     TMF_TRY(tmf_c1_bn_pool_fwd(vol, (const float*)wf, v.scale, v.shift, (float*)o, d->B, L.D, L.H, L.W,
                                                     L.cout, d->slope[l], stream));
+            } else if (L.route) {
+                TMF_TRY(tmf_bn_act_pool_fwd_route((const float*)z, v.scale, v.shift, (float*)o, (float*)(base + L.off_zsel), d->B, L.D, L.H,
+                                                  L.W, L.cout, d->slope[l], stream));
             } else {
                 TMF_TRY(tmf_bn_act_pool_fwd_t(z, v.scale, v.shift, o, d->B, L.D, L.H, L.W, L.cout, L.pool, d->slope[l],
                                               (L.z16 ? 1 : 0) | (L.o16 ? 2 : 0), stream));
@@ -265,7 +279,7 @@ extern "C" size_t tmf_snet_eval_workspace_bytes(const tmf_snet_desc* d) {
     const TmfAlgoScope algo_scope(d->flags);
     tmf_snet_desc e = *d;
     if (e.precision == TMF_PREC_FP32X) { e.precision = TMF_PREC_FP32; e.storage_bf16 = 0; }
-    return make_plan(e).saved_bytes;            // same carving: raw conv outputs (bf16 modes), block outputs, vectors, packed weights
+    return make_plan(e, false).saved_bytes;     // same carving: raw conv outputs (bf16 modes), block outputs, vectors, packed weights
 }
 
 extern "C" int tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const tmf_snet_params* prm,
@@ -276,7 +290,7 @@ extern "C" int tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const
                 "tmf_snet_eval_fwd: fp32 and bf16 precisions only");
     TMF_REQUIRE_PTR(vol); TMF_REQUIRE_PTR(prm); TMF_REQUIRE_PTR(workspace); TMF_REQUIRE_PTR(out);
     TMF_REQUIRE_ALIGNED(vol); TMF_REQUIRE_ALIGNED(workspace); TMF_REQUIRE_ALIGNED(out);
-    const Plan p = make_plan(*d);
+    const Plan p = make_plan(*d, false);
     TMF_REQUIRE(workspace_bytes >= p.saved_bytes, TMF_E_WORKSPACE, "tmf_snet_eval_fwd: workspace %zu B < required %zu B",
                 workspace_bytes, p.saved_bytes);
     for (int l = 0; l < NL; ++l)
@@ -384,6 +398,10 @@ extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, cons
             if (b16) TMF_TRY(tmf_c1_bwd_fused_bf16(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, go, base + p.off_c1gram,
                                                    g->dweight[l], g->dgamma[l], g->dbeta[l], ws, p.ws_bytes, d->B, L.D, L.H, L.W, L.cout,
                                                    d->slope[l], L.o16 ? 1 : 0, TMF_DW_REFERENCE, stream));
+            else if (L.route) TMF_TRY(tmf_c1_bwd_fused_route(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, (const float*)go,
+                                                             (const float*)(base + L.off_zsel), (const unsigned char*)(base + L.off_arg),
+                                                             base + p.off_c1gram, g->dweight[l], g->dgamma[l], g->dbeta[l], ws, p.ws_bytes,
+                                                             d->B, L.D, L.H, L.W, L.cout, d->slope[l], TMF_DW_REFERENCE, stream));
             else     TMF_TRY(tmf_c1_bwd_fused(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, (const float*)go,
                                               base + p.off_c1gram, g->dweight[l], g->dgamma[l], g->dbeta[l], ws, p.ws_bytes, d->B, L.D,
                                               L.H, L.W, L.cout, d->slope[l], TMF_DW_REFERENCE, stream));
@@ -408,8 +426,10 @@ extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, cons
         }
         const int io = (L.z16 ? 1 : 0) | (L.o16 ? 2 : 0);
         const int nblk = tmf_bn_act_pool_bwd_blocks(d->B, L.D, L.H, L.W, L.cout, L.pool);
-        TMF_TRY(tmf_bn_act_pool_bwd_reduce_t(z, go, v.scale, v.shift, v.mean, v.invstd, part, d->B, L.D, L.H, L.W, L.cout, L.pool,
-                                             d->slope[l], io, stream));
+        if (L.route) TMF_TRY(tmf_bn_act_pool_bwd_reduce_route((const float*)(base + L.off_zsel), (const float*)go, v.scale, v.shift, v.mean,
+                                                              v.invstd, part, d->B, L.D, L.H, L.W, L.cout, d->slope[l], stream));
+        else TMF_TRY(tmf_bn_act_pool_bwd_reduce_t(z, go, v.scale, v.shift, v.mean, v.invstd, part, d->B, L.D, L.H, L.W, L.cout, L.pool,
+                                                  d->slope[l], io, stream));
         TMF_TRY(tmf_bn_bwd_finalize(part, nblk, L.cout, count, g->dgamma[l], g->dbeta[l], coef, stream));
         TMF_TRY(tmf_bn_act_pool_bwd_apply_t(z, go, v.scale, v.shift, v.mean, v.invstd, coef, dz, d->B, L.D, L.H, L.W, L.cout,
                                             L.pool, d->slope[l], io, stream));

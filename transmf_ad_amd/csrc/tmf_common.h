@@ -90,7 +90,7 @@ int tmf_conv3d_stat_blocks_mode(int B, int D, int H, int W, int cin, int cout, i
 // Process options (options.hip: one table row each; include/tmf_hip.h documents them).  tmf_opt: the value in effect — the
 // calling entry's choice for the options of the per-call word (below), else tmf_set_option's, else the environment's, else the default.
 enum TmfOpt {
-    TMF_OPT_CONV_WINO, TMF_OPT_WINO_P, TMF_OPT_WINO_X, TMF_OPT_C1_GRAM, TMF_OPT_C1_SPLIT,       // (also per call)
+    TMF_OPT_CONV_WINO, TMF_OPT_WINO_P, TMF_OPT_WINO_X, TMF_OPT_C1_GRAM, TMF_OPT_C1_SPLIT, TMF_OPT_POOL_RECOMPUTE,   // (also per call)
     TMF_OPT_WINO_CUS, TMF_OPT_CONV_RT, TMF_OPT_CONV_WAVES, TMF_OPT_BF16_V2, TMF_OPT_BF16_DMA, TMF_OPT_WGRAD_TR, TMF_OPT_DEBUG,
     TMF_OPT_WINO_EVEN, TMF_OPT_WINOX_SWAP, TMF_OPT_BF_NT2, TMF_OPT_CONV_AUTO, TMF_OPT_C1_BLOCKS, TMF_OPT_C1_FWD_MULT,   // (environment only)
     TMF_OPT_COUNT

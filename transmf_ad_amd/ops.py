@@ -668,11 +668,11 @@ def _publish_flat_grads(flat, param_ptrs, views, segments) -> None:
 def snet_algo_flags(algo=None) -> int:
     """The algorithm word of a tmf_snet_desc (include/tmf_hip.h: TMF_SNET_ALGO | ...).  algo None: the process options of the
     moment (tmf_set_option / TMF_* environment), pinned for the call — a backward then runs the plan its forward laid out whatever
-    happens to the options in between; a dict {conv_wino: 0..3, wino_p: 0|1, wino_x: 0|1, c1_gram: 0|1|2, c1_split: 0|1} (missing keys: the process
+    happens to the options in between; a dict {conv_wino: 0..3, wino_p: 0|1, wino_x: 0|1, c1_gram: 0|1|2, c1_split: 0|1, pool_recompute: 0..3} (missing keys: the process
     option) is ONE module's own choice (sNet.set_algorithm): two models with different settings live side by side."""
     f = _lib.query("tmf_snet_algo_flags")
     if algo:
-        bad = set(algo) - {"conv_wino", "wino_p", "wino_x", "c1_gram", "c1_split"}
+        bad = set(algo) - {"conv_wino", "wino_p", "wino_x", "c1_gram", "c1_split", "pool_recompute"}
         if bad:
             raise ValueError(f"unknown algorithm option(s) {sorted(bad)}")
         if "conv_wino" in algo:
@@ -684,6 +684,10 @@ def snet_algo_flags(algo=None) -> int:
                 f = (f | bit) if algo[key] else (f & ~bit)
         if "c1_gram" in algo:                            # 2: the bf16 mode's first block through the Gram matrix as well
             f = (f | 0x4000) if algo["c1_gram"] == 2 else (f & ~0x4000)
+        if "pool_recompute" in algo:                     # 1: the pool routing recomputed in backward; 2 / 3: in block 0 / blocks 2, 4 only
+            if algo["pool_recompute"] not in (0, 1, 2, 3):
+                raise ValueError("pool_recompute must be 0, 1, 2 or 3")
+            f = (f & ~0x30000) | {0: 0, 1: 0x30000, 2: 0x10000, 3: 0x20000}[int(algo["pool_recompute"])]
     return f
 
 
@@ -702,6 +706,8 @@ class SNetTrain(torch.autograd.Function):
         B, _, D, H, W = vol.shape
         desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision={"fp32": 0, "bf16": 1, "fp32x": 2}[mode], storage_bf16=int(act16),
                              flags=(_lib.SNET_ALONE if (len(cfg) > 5 and cfg[5]) else 0) | snet_algo_flags(cfg[6] if len(cfg) > 6 else None))
+        if not any(ctx.needs_input_grad[3:]):
+            desc.flags |= 0x30000              # no backward will follow (no_grad, frozen encoder): keep no pool routing in `saved`
         prm = _lib.SnetParams()
         for l in range(7):
             desc.momentum[l], desc.eps[l], desc.slope[l] = momentum[l], eps[l], slope[l]
