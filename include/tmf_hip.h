@@ -735,6 +735,19 @@ int    tmf_adam_step(int n, float* const* params, const float* const* grads, con
                      float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
                      double weight_decay, int step, void* stream);
 
+/* ---- optimizer step: torch.optim.SGD (weight decay, momentum) over ALL parameter tensors in one launch -----------------
+ * reference: utils/utils.py:34-37 (getOptimizer with --optimizer SGD: lr, weight_decay; options/option.py:32,35),
+ * kfold_train_Mnet.py:85 (SGD(lr=0.001, momentum=0.9)).  g' = g + weight_decay p;  momentum == 0: p -= lr g';  otherwise
+ * buf = g' for a tensor without a momentum buffer yet (torch: a clone of g', not scaled), else buf = momentum buf + g';
+ * p -= lr buf.  dampening, nesterov and maximize are not offered (no reference caller uses them).
+ * params / grads / numel / n: as for tmf_adam_step (grads[i] == NULL skips tensor i).  momentum_buf: the momentum buffers of
+ * ALL tensors in one flat caller-owned buffer of tmf_adam_state_elems(n, numel) floats in that function's layout; it needs
+ * no initial fill.  no_buffer_yet: n ints in HOST memory, non-zero for a tensor whose buffer holds nothing yet; tensors of both
+ * kinds share the launch.  The caller clears the flag of every tensor that had a gradient after the call.  momentum_buf and
+ * no_buffer_yet may be NULL exactly when momentum == 0 (they are not read then). */
+int    tmf_sgd_step(int n, float* const* params, const float* const* grads, const long* numel, float* momentum_buf,
+                    const int* no_buffer_yet, double lr, double momentum, double weight_decay, void* stream);
+
 /* ---- losses (csrc/losses.hip) -------------------------------------------------------------------------------------
  * FALoss, reference models/losses.py:122-128: two (B, N, N) similarity matrices F^T F (N = h*w*d tokens of a
  * (B, C, h, w, d) map), their difference D and F.l1_loss over it.  Here D is formed tile by tile on the matrix pipe and never

@@ -220,6 +220,7 @@ PROTOTYPES.update({
                            C.POINTER(HeadsGrads), _p, _p, _p, _f, _p, _z, _p]),
     "tmf_adam_state_elems": (_l, [_i, C.POINTER(_l)]),
     "tmf_adam_step": (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_l), _p, _p, _d, _d, _d, _d, _d, _i, _p]),
+    "tmf_sgd_step": (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_l), _p, C.POINTER(_i), _d, _d, _d, _p]),
 })
 ADAM_MAX_TENSORS = 160
 

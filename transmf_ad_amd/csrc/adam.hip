@@ -10,32 +10,18 @@
 // Update (torch.optim.Adam, amsgrad = False, maximize = False; weight_decay is L2 as in torch):
 //   g' = g + wd * p;  m = m + (1 - b1) (g' - m);  v = b2 v + (1 - b2) g' g';
 //   p = p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-#include "tmf_common.h"
+#include "tmf_optim.h"
 
 namespace {
 
-constexpr int CHUNK = 2048;                    // elements per workgroup: 256 threads x 2 float4
-
-struct AdamTable {
-    float* p[TMF_ADAM_MAX_TENSORS];
-    const float* g[TMF_ADAM_MAX_TENSORS];
-    int off[TMF_ADAM_MAX_TENSORS];             // element offset of the tensor's moments in the flat buffers
-    int first[TMF_ADAM_MAX_TENSORS + 1];       // first chunk of tensor i (prefix sums); first[n] = number of chunks
-    int numel[TMF_ADAM_MAX_TENSORS];
-    int n;
-};
-static_assert(sizeof(AdamTable) <= 6144, "the table is a kernel argument (AMD kernarg segments are not limited to 4 KB)");
+constexpr int CHUNK = TMF_OPT_CHUNK;
+using AdamTable = TmfTensorTable;              // the table, its search and its host loop are shared with sgd.hip (tmf_optim.h)
 
 __global__ __launch_bounds__(256) void adam_step_kernel(const AdamTable t, float* __restrict__ m_, float* __restrict__ v_,
                                                         float step_size, float inv_sqrt_bc2, float omb1, float b2, float omb2,
                                                         float eps, float wd) {
     const int chunk = blockIdx.x;
-    int lo = 0, hi = t.n - 1;                  // the tensor whose chunk range contains `chunk`
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (t.first[mid] <= chunk) lo = mid; else hi = mid - 1;
-    }
-    const int ti = lo;
+    const int ti = tmf_table_find(t, chunk);
     const int base = (chunk - t.first[ti]) * CHUNK;
     const int n = t.numel[ti];
     float* __restrict__ p = t.p[ti];
@@ -83,22 +69,9 @@ extern "C" int tmf_adam_step(int n, float* const* params, const float* const* gr
                 TMF_E_ARG, "tmf_adam_step: lr=%g betas=(%g, %g) eps=%g weight_decay=%g", lr, beta1, beta2, eps, weight_decay);
     TMF_REQUIRE_ALIGNED(exp_avg); TMF_REQUIRE_ALIGNED(exp_avg_sq);
     AdamTable t;
-    long off = 0;
-    int chunks = 0, k = 0;
-    for (int i = 0; i < n; ++i) {
-        TMF_REQUIRE(numel[i] >= 0 && numel[i] < (1L << 31), TMF_E_SHAPE, "tmf_adam_step: tensor %d has %ld elements", i, numel[i]);
-        if (grads[i] != nullptr && numel[i] > 0) {             // a parameter without a gradient is skipped, as in torch
-            TMF_REQUIRE(params[i] != nullptr, TMF_E_NULL, "tmf_adam_step: parameter %d is NULL", i);
-            t.p[k] = params[i]; t.g[k] = grads[i]; t.off[k] = (int)off; t.numel[k] = (int)numel[i]; t.first[k] = chunks;
-            chunks += (int)((numel[i] + CHUNK - 1) / CHUNK);
-            ++k;
-        }
-        off += (numel[i] + 3) & ~3L;                           // every tensor's moments start 16-byte aligned
-        TMF_REQUIRE(off < (1L << 31), TMF_E_SHAPE, "tmf_adam_step: more than 2^31 moment elements");
-    }
-    if (k == 0) return TMF_OK;
-    t.first[k] = chunks;
-    t.n = k;
+    int chunks = 0;
+    TMF_TRY(tmf_table_fill("tmf_adam_step", n, params, grads, numel, t, &chunks, nullptr));
+    if (t.n == 0) return TMF_OK;
     const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
     hipLaunchKernelGGL(adam_step_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, t, exp_avg, exp_avg_sq,
                        (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
@@ -106,10 +79,11 @@ extern "C" int tmf_adam_step(int n, float* const* params, const float* const* gr
     return tmf_launch_result("tmf_adam_step");
 }
 
-// elements of the flat moment buffers tmf_adam_step addresses for these tensors (each tensor padded to a multiple of 4)
+// elements of the flat state buffers tmf_adam_step and tmf_sgd_step address for these tensors (each tensor padded to a
+// multiple of 4)
 extern "C" long tmf_adam_state_elems(int n, const long* numel) {
     if (n <= 0 || numel == nullptr) return 0;
     long off = 0;
-    for (int i = 0; i < n; ++i) off += (numel[i] + 3) & ~3L;
+    for (int i = 0; i < n; ++i) off += tmf_state_padded(numel[i]);
     return off;
 }
