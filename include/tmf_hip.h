@@ -779,6 +779,53 @@ int    tmf_supcon_fwd(const float* features, const long long* labels, const floa
                       int bs, int views, int d, int anchors_all, float temperature, float base_temperature, void* stream);
 int    tmf_supcon_bwd(const float* gfeat, const float* grad_out, float* dfeat, int bs, int views, int d, void* stream);
 
+/* ---- criterion and epoch metrics (csrc/criterion.hip) --------------------------------------------------------------
+ * Cross entropy, reference kfold_train_adversarial.py:94 / kfold_train_single.py:87 (torch.nn.CrossEntropyLoss(), optionally
+ * weight=...) and its call sites :119, :125, :159.  logits: fp32 [B][C] contiguous; target: int64 [B] class indices, -100
+ * (torch's default ignore_index) counts with weight 0, any other value outside [0, C) makes the loss NaN and its gradient
+ * row zero; weight: NULL or C floats.  reduction: 0 'mean' (torch's: sum w[y_i] l_i / sum w[y_i]), 1 'sum'.  loss: one
+ * float.  g (NULL: no gradient wanted): dloss / dlogits [B][C]; tmf_ce_bwd forms dlogits = grad_out[0] * g, grad_out a
+ * device scalar.  Accurate expf / logf, the row maximum subtracted first; sums over samples in double in a fixed order.
+ * tmf_ce_ok: 1 when 1 <= B <= 4096 and 2 <= C <= 16.  One launch each, one workgroup forward. */
+int    tmf_ce_ok(int B, int C);
+int    tmf_ce_fwd(const float* logits, const long long* target, const float* weight, float* loss, float* g, int B, int C,
+                  int reduction, void* stream);
+int    tmf_ce_bwd(const float* g, const float* grad_out, float* dlogits, int B, int C, void* stream);
+/* The whole criterion of kfold_train_adversarial.py:119-125 in one launch: losses[0] = CE(logits, label) ('mean', weight
+ * NULL or C floats), losses[1] = (CE(d_mri, all ones) + CE(d_pet, all zeros)) / 2.  d_mri, d_pet: fp32 [B][2] (the domain
+ * discriminator's logits); their targets are formed in the kernel.  g_logits [B][C], g_mri, g_pet [B][2] (all three or
+ * none): the gradient of losses[0] (g_logits) or of losses[1] (g_mri, g_pet: the 1/2 included) by its own logits.
+ * tmf_adv_criterion_bwd, replacing the autograd backward of :131-132: dlogits = grad_ce[0] * g_logits, dmri = grad_ad[0] *
+ * g_mri, dpet = grad_ad[0] * g_pet in one launch; grad_ce, grad_ad: device scalars, NULL meaning zero. */
+int    tmf_adv_criterion_fwd(const float* logits, const float* d_mri, const float* d_pet, const long long* label,
+                             const float* weight, float* losses, float* g_logits, float* g_mri, float* g_pet, int B, int C,
+                             void* stream);
+int    tmf_adv_criterion_bwd(const float* g_logits, const float* g_mri, const float* g_pet, const float* grad_ce,
+                             const float* grad_ad, float* dlogits, float* dmri, float* dpet, int B, int C, void* stream);
+/* The trainer's metrics of kfold_train_adversarial.py:178-182 (ignite Accuracy of the three heads, Average of the two
+ * losses read at :127-128) as one read-add-write of a device state: one launch, one workgroup; calls on one stream
+ * serialize, the caller zeroes the state to reset.  state: 8 words of 8 bytes, 8-byte aligned — [0] updates, [1] samples
+ * (int64); [2] sum of losses[0], [3] sum of losses[1] (double); [4], [5], [6] samples whose argmax (the first maximal
+ * index; a NaN counts as the maximum, as in torch.argmax) equals the target, for logits / label, d_mri / 1, d_pet / 0
+ * (int64); [7] unused.  losses: the two device floats of tmf_adv_criterion_fwd. */
+int    tmf_train_metrics_update(void* state, const float* losses, const float* logits, const float* d_mri, const float* d_pet,
+                                const long long* label, int B, int C, void* stream);
+/* The evaluator's metrics of :183-187 (ignite Accuracy, ConfusionMatrix, ROC_AUC, Loss): one launch, one workgroup.
+ * state: (2 + C * C) words of 8 bytes — [0] sum of the per-sample cross entropy (double), [1] samples (int64),
+ * [2 + t * C + p] samples of true class t predicted as p = argmax (int64; row true, column predicted: the convention of
+ * ignite, scikit-learn and utils/utils.py:44-51).  scores[offset + i] = softmax(logits_i)[C - 1] (fp32),
+ * labels_out[offset + i] = label[i]: the epoch buffers tmf_auc reads; the host keeps `offset`. */
+int    tmf_eval_metrics_update(void* state, float* scores, long long* labels_out, long offset, const float* logits,
+                               const long long* label, int B, int C, void* stream);
+/* Exact ROC AUC (ignite ROC_AUC -> sklearn.metrics.roc_auc_score) as the Mann-Whitney statistic in integers:
+ * out[0] = T = sum over (positive i, negative j) of 2 [s_i > s_j] + [s_i == s_j], out[1] = P, out[2] = N (uint64; a label
+ * of 0 is negative, any other positive); AUC = T / (2 P N), formed by the host in double.  Pair tiles over many workgroups,
+ * per-workgroup counts in `workspace` (tmf_auc_workspace_bytes(n) bytes, 8-byte aligned), summed by a second launch:
+ * integer counts, so the result does not depend on any order.  tmf_auc_ok: 1 when 1 <= n <= 65536. */
+int    tmf_auc_ok(long n);
+size_t tmf_auc_workspace_bytes(long n);
+int    tmf_auc(const float* scores, const long long* labels, long n, void* workspace, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

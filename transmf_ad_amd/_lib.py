@@ -259,6 +259,20 @@ PROTOTYPES.update({
     "tmf_supcon_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
 })
 
+PROTOTYPES.update({
+    "tmf_ce_ok": (_i, [_i, _i]),
+    "tmf_ce_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "tmf_ce_bwd": (_i, [_p, _p, _p, _i, _i, _p]),
+    "tmf_adv_criterion_fwd": (_i, [_p] * 9 + [_i, _i, _p]),
+    "tmf_adv_criterion_bwd": (_i, [_p] * 8 + [_i, _i, _p]),
+    "tmf_train_metrics_update": (_i, [_p] * 6 + [_i, _i, _p]),
+    "tmf_eval_metrics_update": (_i, [_p, _p, _p, _l, _p, _p, _i, _i, _p]),
+    "tmf_auc_ok": (_i, [_l]),
+    "tmf_auc_workspace_bytes": (_z, [_l]),
+    "tmf_auc": (_i, [_p, _p, _l, _p, _p, _p]),
+})
+TRAIN_METRICS_WORDS = 8      # the state of tmf_train_metrics_update
+
 _lib = None
 
 

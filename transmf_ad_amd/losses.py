@@ -15,6 +15,15 @@ SupConLoss:  anchors a_i, contrast rows c_j (all views of all samples, view-majo
 column is left out of the log-sum-exp and of the positives m_ij;
 loss_i = -(T / T_base) sum_j m_ij (l_ij - log sum_{k != i} exp l_ik) / sum_j m_ij;  the result is the mean over anchors.
 An anchor without a positive gives 0 / 0 = NaN, as in the reference.
+
+CrossEntropyLoss and AdversarialCriterion (csrc/criterion.hip): the step's criterion.
+
+    from transmf_ad_amd.losses import CrossEntropyLoss, AdversarialCriterion
+
+CrossEntropyLoss has torch.nn.CrossEntropyLoss's constructor; AdversarialCriterion()(output_logits, D_MRI_logits,
+D_PET_logits, label) returns (ce_loss, ad_loss) of kfold_train_adversarial.py:119-125 from one launch.  fp32 (B, C) logits
+and int64 targets on a HIP device take the kernels (``ce_kernel_ok`` / ``adversarial_kernel_ok`` tell), every other call
+F.cross_entropy.
 """
 from __future__ import annotations
 
@@ -169,3 +178,77 @@ class SupConLoss(torch.nn.Module):
         else:
             base = torch.eye(bs, dtype=torch.float32, device=dev)
         return supcon_loss_torch(features, base, anchors_all, self.temperature, self.base_temperature)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CrossEntropyLoss and the adversarial criterion (csrc/criterion.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def ce_shape_ok(B, C):
+    """Whether the kernels cover B rows of C classes: tmf_ce_ok."""
+    return bool(_lib.query("tmf_ce_ok", int(B), int(C)))
+
+
+def ce_kernel_ok(logits, target, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
+    """True when CrossEntropyLoss(weight, ignore_index=..., reduction=..., label_smoothing=...)(logits, target) runs on the
+    kernels: fp32 (B, C) logits and int64 (B,) class indices on one HIP device, the default ignore_index and
+    label_smoothing, 'mean' or 'sum'."""
+    if reduction not in _REDUCTION or ignore_index != -100 or label_smoothing != 0.0:
+        return False
+    if not _on_hip_fp32(logits) or logits.dim() != 2 or not torch.is_tensor(target):
+        return False
+    if target.dtype != torch.int64 or target.device != logits.device or target.shape != logits.shape[:1]:
+        return False
+    if weight is not None and not (_on_hip_fp32(weight) and weight.device == logits.device
+                                   and weight.shape == logits.shape[1:]):
+        return False
+    return ce_shape_ok(logits.shape[0], logits.shape[1])
+
+
+class CrossEntropyLoss(torch.nn.CrossEntropyLoss):
+    """torch.nn.CrossEntropyLoss (same constructor) on tmf_ce_fwd / tmf_ce_bwd: one launch forward, one backward.  Every call
+    the kernels do not cover (``ce_kernel_ok``) runs F.cross_entropy with the same arguments."""
+
+    def forward(self, input, target):
+        if not ce_kernel_ok(input, target, self.weight, self.ignore_index, self.reduction, self.label_smoothing):
+            return F.cross_entropy(input, target, weight=self.weight, ignore_index=self.ignore_index,
+                                   reduction=self.reduction, label_smoothing=self.label_smoothing)
+        weight = None if self.weight is None else self.weight.contiguous()
+        with torch.cuda.device(input.device):
+            return ops.cross_entropy(input, target.contiguous(), weight, _REDUCTION[self.reduction])
+
+
+def adversarial_criterion_torch(output_logits, D_MRI_logits, D_PET_logits, label, weight=None):
+    """The criterion of kfold_train_adversarial.py:119-125 in torch ops: (ce_loss, ad_loss)."""
+    ce_loss = F.cross_entropy(output_logits, label, weight=weight)
+    mri_gt = torch.ones(D_MRI_logits.shape[0], dtype=torch.int64, device=D_MRI_logits.device)
+    pet_gt = torch.zeros(D_PET_logits.shape[0], dtype=torch.int64, device=D_PET_logits.device)
+    ad_loss = (F.cross_entropy(D_MRI_logits, mri_gt) + F.cross_entropy(D_PET_logits, pet_gt)) / 2
+    return ce_loss, ad_loss
+
+
+def adversarial_kernel_ok(output_logits, D_MRI_logits, D_PET_logits, label, weight=None):
+    """True when AdversarialCriterion(weight)(...) runs on the one-launch kernel: the label head as for ``ce_kernel_ok``, the
+    two domain heads fp32 (B, 2) on the same device."""
+    if not ce_kernel_ok(output_logits, label, weight):
+        return False
+    want = (output_logits.shape[0], 2)
+    return all(_on_hip_fp32(d) and d.device == output_logits.device and tuple(d.shape) == want
+               for d in (D_MRI_logits, D_PET_logits))
+
+
+class AdversarialCriterion(torch.nn.Module):
+    """``ce_loss, ad_loss = criterion(output_logits, D_MRI_logits, D_PET_logits, label)``: CE(output_logits, label) and
+    (CE(D_MRI_logits, ones) + CE(D_PET_logits, zeros)) / 2, two 0-dim views of one 2-float device tensor (``.base``) from one
+    launch; ``(ad_loss + ce_loss).backward()`` is one more.  ``weight`` weighs the classes of the label head."""
+
+    def __init__(self, weight=None):
+        super().__init__()
+        self.register_buffer("weight", weight)
+
+    def forward(self, output_logits, D_MRI_logits, D_PET_logits, label):
+        if not adversarial_kernel_ok(output_logits, D_MRI_logits, D_PET_logits, label, self.weight):
+            return adversarial_criterion_torch(output_logits, D_MRI_logits, D_PET_logits, label, self.weight)
+        weight = None if self.weight is None else self.weight.contiguous()
+        with torch.cuda.device(output_logits.device):
+            return ops.adversarial_criterion(output_logits, D_MRI_logits, D_PET_logits, label.contiguous(), weight)

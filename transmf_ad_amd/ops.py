@@ -1559,3 +1559,89 @@ class SupConLossFn(torch.autograd.Function):
 
 def supcon_loss(features, labels, mask, anchors_all, temperature, base_temperature):
     return SupConLossFn.apply(features, labels, mask, anchors_all, temperature, base_temperature)
+
+
+# --------------------------------------------------------------------------------------
+# criterion and epoch metrics                       (kfold_train_adversarial.py:119-131, 178-194)
+# --------------------------------------------------------------------------------------
+
+class CrossEntropyFn(torch.autograd.Function):
+    """F.cross_entropy over fp32 (B, C) logits and int64 targets, reduction 0 mean | 1 sum (tmf_ce_fwd): one launch that
+    also leaves dloss / dlogits when a gradient is wanted; the backward scales it by grad_output (tmf_ce_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, reduction):
+        logits = _chk(logits, "input")
+        B, C = logits.shape
+        want = ctx.needs_input_grad[0]
+        loss = torch.empty((), device=logits.device, dtype=_f32)
+        g = torch.empty_like(logits) if want else None
+        _lib.call("tmf_ce_fwd", logits.data_ptr(), target.data_ptr(), _ptr(weight), loss.data_ptr(), _ptr(g), B, C, reduction,
+                  _stream())
+        if want:
+            ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (g,) = ctx.saved_tensors
+        dloss = _chk(dloss, "grad_output")
+        d = torch.empty_like(g)
+        _lib.call("tmf_ce_bwd", g.data_ptr(), dloss.data_ptr(), d.data_ptr(), g.shape[0], g.shape[1], _stream())
+        return d, None, None, None
+
+
+def cross_entropy(logits, target, weight, reduction):
+    return CrossEntropyFn.apply(logits, target, weight, reduction)
+
+
+class AdversarialCriterionFn(torch.autograd.Function):
+    """(CE(logits, label), (CE(d_mri, 1) + CE(d_pet, 0)) / 2) as two 0-dim views of one 2-float tensor, in one launch
+    (tmf_adv_criterion_fwd); the backward takes the two grads — either may be absent — and makes one launch."""
+
+    @staticmethod
+    def forward(ctx, logits, d_mri, d_pet, label, weight):
+        logits, d_mri, d_pet = _chk(logits, "output_logits"), _chk(d_mri, "D_MRI_logits"), _chk(d_pet, "D_PET_logits")
+        B, C = logits.shape
+        want = any(ctx.needs_input_grad[:3])
+        losses = torch.empty(2, device=logits.device, dtype=_f32)
+        gs = (torch.empty_like(logits), torch.empty_like(d_mri), torch.empty_like(d_pet)) if want else (None, None, None)
+        _lib.call("tmf_adv_criterion_fwd", logits.data_ptr(), d_mri.data_ptr(), d_pet.data_ptr(), label.data_ptr(), _ptr(weight),
+                  losses.data_ptr(), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), B, C, _stream())
+        if want:
+            ctx.save_for_backward(*gs)
+        ctx.set_materialize_grads(False)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, d_ce, d_ad):
+        g0, g1, g2 = ctx.saved_tensors
+        d_ce = None if d_ce is None else _chk(d_ce, "grad of ce_loss")
+        d_ad = None if d_ad is None else _chk(d_ad, "grad of ad_loss")
+        d0, d1, d2 = torch.empty_like(g0), torch.empty_like(g1), torch.empty_like(g2)
+        _lib.call("tmf_adv_criterion_bwd", g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), _ptr(d_ce), _ptr(d_ad), d0.data_ptr(),
+                  d1.data_ptr(), d2.data_ptr(), g0.shape[0], g0.shape[1], _stream())
+        return d0, d1, d2, None, None
+
+
+def adversarial_criterion(logits, d_mri, d_pet, label, weight):
+    return AdversarialCriterionFn.apply(logits, d_mri, d_pet, label, weight)
+
+
+def train_metrics_update(state, losses, logits, d_mri, d_pet, label):
+    """One read-add-write of the (8,) int64 device state (tmf_train_metrics_update); losses: the 2-float device tensor."""
+    logits, d_mri, d_pet = _chk(logits, "output_logits"), _chk(d_mri, "D_MRI_logits"), _chk(d_pet, "D_PET_logits")
+    _lib.call("tmf_train_metrics_update", state.data_ptr(), losses.data_ptr(), logits.data_ptr(), d_mri.data_ptr(),
+              d_pet.data_ptr(), label.data_ptr(), logits.shape[0], logits.shape[1], _stream())
+
+
+def eval_metrics_update(state, scores, labels, offset, logits, label):
+    """tmf_eval_metrics_update: loss sum and confusion counts into `state`, scores / labels at `offset` of the epoch buffers."""
+    logits = _chk(logits, "logits")
+    _lib.call("tmf_eval_metrics_update", state.data_ptr(), scores.data_ptr(), labels.data_ptr(), int(offset), logits.data_ptr(),
+              label.data_ptr(), logits.shape[0], logits.shape[1], _stream())
+
+
+def auc_counts(scores, labels, n, workspace, out):
+    """tmf_auc over the first n entries of the epoch buffers: T, P, N (uint64) into the three int64 words of `out`."""
+    _lib.call("tmf_auc", scores.data_ptr(), labels.data_ptr(), int(n), workspace.data_ptr(), out.data_ptr(), _stream())
