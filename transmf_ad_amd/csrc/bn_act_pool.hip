@@ -203,8 +203,11 @@ struct Window {
     }
 };
 
+#define TMF_BN_RED_F32_ROWS 32      // longest cross-row sum of bn_bwd_reduce_kernel that stays an fp32 chain (see its end)
+
 // ROUTE (max pool): `z` is the forward's z_sel (pooled shape) — one read per window instead of eight, the same sums
-template <int VEC, int POOL, typename ZT = float, typename YT = float, bool ROUTE = false>
+// LONG: more than TMF_BN_RED_F32_ROWS rows (chosen by the launch, so the short form's code is untouched by the fp64 sum)
+template <int VEC, int POOL, typename ZT = float, typename YT = float, bool ROUTE = false, bool LONG = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     const ZT* __restrict__ z, const YT* __restrict__ dout, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -287,8 +290,19 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     }
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * g.C; e += blockDim.x) {
+        // Few channels make many rows (256 at C = 4, 85 at C = 12): summed one after the other in fp32 they were the one long
+        // fp32 chain between the per-thread sums and the fp64 finalize, at 85 rows 4.3-4.6 x the error of a pairwise fp32 sum
+        // (tests/test_gpu_bn_reduce.py, family B).  Above TMF_BN_RED_F32_ROWS rows (LONG) the chain runs in fp64 and leaves one
+        // rounding per slab element; up to it (C >= 32 at 4 channels per lane, C >= 64 at 8: every block of a dim-128
+        // encoder) the fp32 chain stays as it was, within that bound, and so does every bit of those results.
         float a = 0.f;
-        for (int r = 0; r < ROWS; ++r) a += red[r * 2 * g.C + e];
+        if constexpr (LONG) {
+            double a64 = 0.0;
+            for (int r = 0; r < ROWS; ++r) a64 += (double)red[r * 2 * g.C + e];
+            a = (float)a64;
+        } else {
+            for (int r = 0; r < ROWS; ++r) a += red[r * 2 * g.C + e];
+        }
         partial[(size_t)blockIdx.x * 2 * g.C + e] = a;
     }
 }
@@ -590,7 +604,13 @@ extern "C" int tmf_bn_act_pool_bwd_reduce_t(const void* z, const void* dout, con
     EwPlan p = plan_ew(g.nwin, C, io == 3 && pool != TMF_POOL_AVG2);
     p.nblk = plan_ew(g.nwin, C).nblk;            // the slab count callers size `partial` with (tmf_bn_act_pool_bwd_blocks)
     const size_t lds = (size_t)p.rows * 2 * C * 4;
-#define K_RED(V, P, ...) hipLaunchKernelGGL((bn_bwd_reduce_kernel<V, P, ZT_, YT_>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream, __VA_ARGS__)
+#define K_RED(V, P, ...)                                                                                                                        \
+    do {                                                                                                                                        \
+        if (p.rows > TMF_BN_RED_F32_ROWS)                                                                                                       \
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<V, P, ZT_, YT_, false, true>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream, __VA_ARGS__); \
+        else                                                                                                                                    \
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<V, P, ZT_, YT_>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream, __VA_ARGS__);         \
+    } while (0)
 #define L_RED(ZT, YT) { typedef ZT ZT_; typedef YT YT_; \
         TMF_DISPATCH_VP(K_RED, p.vec, pool, (const ZT_*)z, (const YT_*)dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope); }
     TMF_DISPATCH_IO(L_RED, io, "tmf_bn_act_pool_bwd_reduce_t");
@@ -611,12 +631,13 @@ extern "C" int tmf_bn_act_pool_bwd_reduce_route(const float* z_sel, const float*
     const Geo g = make_geo(B, D, H, W, C, TMF_POOL_MAX2);
     const EwPlan p = plan_ew(g.nwin, C);
     const size_t lds = (size_t)p.rows * 2 * C * 4;
-    if (p.vec == 4)
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<4, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream,
-                           z_sel, dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope);
-    else
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<1, TMF_POOL_MAX2, float, float, true>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream,
-                           z_sel, dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope);
+#define K_RED_ROUTE(V, LONG)                                                                                                               \
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<V, TMF_POOL_MAX2, float, float, true, LONG>), dim3(p.nblk), dim3(256), lds, (hipStream_t)stream, \
+                       z_sel, dout, scale, shift, mean, invstd, partial, g, p.cq, p.rows, slope)
+    const bool lng = p.rows > TMF_BN_RED_F32_ROWS;
+    if (p.vec == 4) { if (lng) K_RED_ROUTE(4, true); else K_RED_ROUTE(4, false); }
+    else { if (lng) K_RED_ROUTE(1, true); else K_RED_ROUTE(1, false); }
+#undef K_RED_ROUTE
     return tmf_launch_result("tmf_bn_act_pool_bwd_reduce_route");
 }
 
