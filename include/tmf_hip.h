@@ -510,6 +510,33 @@ int    tmf_volume_minmax(const float* vol, float* minmax, void* workspace, size_
 int    tmf_scale_flip(const float* src, float* dst, const float* minmax, const unsigned char* flip_d,
                       int B, int D, int H, int W, void* stream);
 
+/* Device-resident data set: one launch writes a whole training batch of both modalities from stores that stay in HBM for
+ * the run.  Replaces the reference's per-batch host pipeline — the CacheDataset of datasets/__init__.py:12-29 and the
+ * DataLoader(num_workers=0) of :56 over the MONAI transforms of datasets/ADNI.py:59-84, built per fold in
+ * kfold_train_adversarial.py:60-66, and the `batch['MRI'].to(device)` copies of :106-108 — with the device as the cache:
+ * store_mri / store_pet [N][D][H][W] fp32 hold every subject AFTER ScaleIntensity (the deterministic part of the transform:
+ * tmf_volume_minmax + tmf_scale_flip without a flip, once per run), labels [N] int64.  For sample b of the batch and both
+ * modalities
+ *     out[b] = zoom_area( rotate_x( flip_d( store[decisions[b].index] ) ) ),   out_label[b] = labels[decisions[b].index],
+ * every stage only where the record applies it, with the formulas — the same fp32 operations in the same order — of
+ * tmf_scale_flip's flip, tmf_rotate_x and tmf_zoom_area: BIT-identical to those three calls in sequence on the gathered
+ * volumes (and so to oracle/input_oracle.py train_transform), without their intermediate tensors.  out_mri / out_pet
+ * [B][D][H][W] fp32, out_label [B] int64; decisions: DEVICE array of B records (the random draws stay with the caller, as
+ * above).  2 B <= 65535, D <= 65535; the outputs may not overlap the stores or each other.
+ * PRECONDITION (the records live on the device, the entry cannot see them): 0 <= index < N, and with od != 0 each of od /
+ * oh / ow in [1, D] / [1, H] / [1, W].  The kernel does not rely on it: a record outside these ranges reads nothing and
+ * yields a NaN volume pair and label -1. */
+typedef struct tmf_augment_decision {      /* 32 bytes */
+    int32_t index;                         /* subject: row of the stores and of labels */
+    int32_t flip;                          /* != 0: reverse the first spatial axis (RandFlipd(spatial_axis=0)) */
+    int32_t do_rot;                        /* != 0: rotate about the first spatial axis by the angle of (cos_a, sin_a) */
+    float   cos_a, sin_a;                  /* cos / sin of the angle, rounded to fp32 on the host (as tmf_rotate_x's cos_sin) */
+    int32_t od, oh, ow;                    /* zoomed size floor(S z) per axis (as tmf_zoom_area's out_size); od == 0: no zoom */
+} tmf_augment_decision;
+int    tmf_batch_augment(const float* store_mri, const float* store_pet, const int64_t* labels,
+                         const tmf_augment_decision* decisions, float* out_mri, float* out_pet, int64_t* out_label,
+                         int N, int B, int D, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------
  * Whole-encoder entries (csrc/snet_path.hip): ONE call enqueues every launch of an sNet train-mode forward, or of its
  * backward.  Replaces, per modality, `self.mri_cnn(mri)` / `self.pet_cnn(pet)` (models/mymodel.py:206-207 ->

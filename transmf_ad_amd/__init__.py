@@ -13,7 +13,7 @@ from .gradient_reversal import GradientReversal, revgrad            # noqa: F401
 from .mymodel import (model_ad, model_CNN, model_CNN_ad, model_single, model_transformer,   # noqa: F401
                       model_transformer_res)
 from .ops import get_conv_precision, set_activation_storage, set_conv_precision   # noqa: F401
-from .pipeline import DevicePrefetcher, scale_intensity_flip, rotate_zoom         # noqa: F401
+from .pipeline import DeviceDataset, DevicePrefetcher, scale_intensity_flip, rotate_zoom   # noqa: F401
 from .nifti import read_nifti, write_nifti, nifti_batches         # noqa: F401
 from . import optim                                                  # noqa: F401
 from .losses import FALoss, SupConLoss                               # noqa: F401
@@ -23,5 +23,5 @@ from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, Fe
 __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_transformer", "model_transformer_res", "sNet",
            "CrossTransformer", "CrossTransformer_MOD_AVG", "Transformer",
            "Attention", "PreNorm", "FeedForward", "revgrad", "GradientReversal", "load_library", "TmfError",
-           "set_conv_precision", "get_conv_precision", "set_activation_storage", "DevicePrefetcher", "scale_intensity_flip", "rotate_zoom",
+           "set_conv_precision", "get_conv_precision", "set_activation_storage", "DeviceDataset", "DevicePrefetcher", "scale_intensity_flip", "rotate_zoom",
            "read_nifti", "write_nifti", "nifti_batches", "FALoss", "SupConLoss"]

@@ -152,6 +152,7 @@ PROTOTYPES.update({
     "tmf_scale_flip": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "tmf_rotate_x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "tmf_zoom_area": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "tmf_batch_augment": (_i, [_p] * 7 + [_i] * 5 + [_p]),
     "tmf_snet_saved_bytes": (_z, [C.POINTER(SnetDesc)]),
     "tmf_snet_bwd_scratch_bytes": (_z, [C.POINTER(SnetDesc)]),
     "tmf_snet_train_fwd": (_i, [C.POINTER(SnetDesc), _p, C.POINTER(SnetParams), _p, _z, _p, _p]),
