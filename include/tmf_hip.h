@@ -682,6 +682,19 @@ int    tmf_fusion_train_bwd(const tmf_fusion_desc* d, const float* mri_tok, cons
                             const tmf_xformer_params* inst, const void* saved, size_t saved_bytes, const float* dcls,
                             const tmf_xformer_grads* grads, float* dmri_tok, float* dpet_tok,
                             void* scratch, size_t scratch_bytes, void* stream);
+/* Forward-only form: `self.fuse_transformer(mri_embeddings, pet_embeddings)` under torch.no_grad() — val_step
+ * (kfold_train_adversarial.py:144-161) and the test run after training (:229-250) — as ONE call that keeps nothing.
+ * Descriptor rules, inst[], TMF_FUSION_PER_OP, the depth range (0 included: pooling only) and the keep-masks (non-NULL
+ * masks are applied: a train-mode module under no_grad) are those of tmf_fusion_train_fwd, and cls is bit-identical to
+ * its cls.  `workspace` (>= tmf_fusion_infer_workspace_bytes, 16-byte aligned) is scratch: never read before it is
+ * written within the call, meaningless after it; mri_tok / pet_tok are not written.  It holds no per-instance
+ * activations — fused geometry: the two running token buffers, the K-row / V-column panels of the current and the next
+ * context, one forward weight pack (4 dim^2 + 2 mlp dim floats) per instance, the pool's argmax; one launch per op: one
+ * instance's intermediates reused by every instance and the running token buffers (size independent of depth). */
+size_t tmf_fusion_infer_workspace_bytes(const tmf_fusion_desc* d);
+int    tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
+                            const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes,
+                            float* cls, void* stream);
 
 /* ------------------------------------------------------------------------------
  * The dense heads of model_ad in one launch per direction (csrc/heads.hip).  Replaces `self.D(D_MRI_inp)`,

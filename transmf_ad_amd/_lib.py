@@ -191,6 +191,8 @@ PROTOTYPES.update({
     "tmf_fusion_train_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
     "tmf_fusion_train_bwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p,
                                   C.POINTER(XformerGrads), _p, _p, _p, _z, _p]),
+    "tmf_fusion_infer_workspace_bytes": (_z, [C.POINTER(FusionDesc)]),
+    "tmf_fusion_infer_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
 })
 
 

@@ -32,7 +32,8 @@ int tmf_xf_part_stride(void);
 int tmf_xf_pack_floats(void);
 int tmf_xf_pack_kv_offset(void);
 int tmf_xf_launch_pack(int n_inst, const tmf_xformer_params* inst, float* const* pk_fwd, float* const* pk_bwd, hipStream_t s);
-int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fwd_io* io, float scale, int only_kv, int h2, hipStream_t s);
+int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fwd_io* io, float scale, int only_kv, int h2, int infer,
+                      hipStream_t s);
 int tmf_xf_launch_bwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_bwd_io* io, float scale, int h2, hipStream_t s);
 int tmf_xf_launch_colsum(int n_inst, const float* const* part, float* const* small, float* const* lnf, int nblk, hipStream_t s);
 
@@ -140,6 +141,51 @@ Plan make_plan(const tmf_fusion_desc& d) {
 
 inline float* F(char* base, size_t off) { return (float*)(base + off); }
 
+// Workspace of the forward-only entry (byte offsets): scratch, nothing in it outlives the call.
+//   fused: the two running token buffers (an instance's y replaces its x in place: a workgroup reads exactly the rows it
+//          later writes, and reads them first), KR / VC of the current and of the next context (two sets, swapped per
+//          instance), one forward weight pack per instance, the pool's argmax.
+//   one launch per op: ONE instance's intermediates (InstPlan offsets q, kv, out, lse, x1, h, g, x2 and the six statistics
+//          — `a` and `f` are never written) reused by every instance, two token buffers per stream (tmf_layernorm_fwd's
+//          residual and output are __restrict__: the output alternates), the pool's argmax.
+struct InferPlan {
+    Plan p;
+    size_t tok[2][2], KR[2], VC[2], pk, slab, arg, bytes;
+};
+
+InferPlan make_infer_plan(const tmf_fusion_desc& d) {
+    InferPlan ip;
+    ip.p = make_plan(d);
+    const Plan& p = ip.p;
+    const size_t R = (size_t)p.R, dim = d.dim, inner = p.inner, mlp = d.mlp;
+    size_t o = 0;
+    auto take = [&](size_t floats) { const size_t at = o; o += up256(floats * 4); return at; };
+    ip.KR[0] = ip.KR[1] = ip.VC[0] = ip.VC[1] = ip.pk = ip.slab = 0;
+    if (p.fused) {
+        ip.tok[0][0] = ip.tok[0][1] = take(R * dim);
+        ip.tok[1][0] = ip.tok[1][1] = take(R * dim);
+        const size_t panel = (size_t)d.B * p.npad * inner;
+        for (int k = 0; k < 2; ++k) { ip.KR[k] = take(panel); ip.VC[k] = take(panel); }
+        ip.pk = o;
+        o += (size_t)(2 * d.depth) * up256((size_t)tmf_xf_pack_floats() * 4);
+    } else {
+        for (int k = 0; k < 2; ++k) { ip.tok[0][k] = take(R * dim); ip.tok[1][k] = take(R * dim); }
+        InstPlan& I = ip.p.I;                   // the same names as the training slab, without a, f, y
+        ip.slab = o;
+        size_t so = 0;
+        auto stake = [&](size_t floats) { const size_t at = so; so += up256(floats * 4); return at; };
+        I.q = stake(R * inner); I.kv = stake(R * 2 * inner); I.out = stake(R * inner);
+        I.lse = stake((size_t)d.B * d.heads * p.npad); I.x1 = stake(R * dim); I.h = stake(R * mlp); I.g = stake(R * mlp);
+        I.x2 = stake(R * dim);
+        I.m1 = stake(R); I.r1 = stake(R); I.m2 = stake(R); I.r2 = stake(R); I.mf = stake(R); I.rf = stake(R);
+        I.total = so;
+        o += so;
+    }
+    ip.arg = take((size_t)d.B * 2 * dim);       // int32 argmax of the max pools (tmf_token_pool_fwd insists on it)
+    ip.bytes = o;
+    return ip;
+}
+
 }  // namespace
 
 extern "C" size_t tmf_fusion_saved_bytes(const tmf_fusion_desc* d) {
@@ -164,14 +210,24 @@ extern "C" size_t tmf_fusion_bwd_scratch_bytes(const tmf_fusion_desc* d) {
     return make_plan(*d).scratch_bytes;
 }
 
+extern "C" size_t tmf_fusion_infer_workspace_bytes(const tmf_fusion_desc* d) {
+    if (check_desc("tmf_fusion_infer_workspace_bytes", d) != TMF_OK) return 0;
+    return make_infer_plan(*d).bytes;
+}
+
 // One Transformer(depth=1) instance:  y = LayerNorm_f( FF(LN2(x1)) + x1 ) + x,   x1 = Attention(LN1(x), ctx) + x
+// y_out != NULL (the forward-only entry): y goes there instead of the slab, and the LayerNorm outputs a / f that only the
+// weight gradients read are not written (the entries take NULL for them); the same launches otherwise.
 static int instance_fwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xformer_params& w, const float* x, const float* c,
-                        char* sv, void* stream) {
+                        char* sv, void* stream, float* y_out = nullptr) {
     const int R = p.R, dim = d.dim, inner = p.inner, mlp = d.mlp;
     const InstPlan& I = p.I;
     const float scale = 1.0f / sqrtf((float)d.dim_head);
+    float* a_out = y_out != nullptr ? nullptr : F(sv, I.a);
+    float* f_out = y_out != nullptr ? nullptr : F(sv, I.f);
+    if (y_out == nullptr) y_out = F(sv, I.y);
     TMF_TRY(tmf_tok_linear_fwd(x, w.wq, nullptr, nullptr, F(sv, I.q), R, dim, inner, w.ln1_g, w.ln1_b, w.eps1, F(sv, I.m1),
-                               F(sv, I.r1), F(sv, I.a), nullptr, stream));
+                               F(sv, I.r1), a_out, nullptr, stream));
     TMF_TRY(tmf_tok_linear_fwd(c, w.wkv, nullptr, nullptr, F(sv, I.kv), R, dim, 2 * inner, nullptr, nullptr, 0.f, nullptr,
                                nullptr, nullptr, nullptr, stream));
     TMF_TRY(tmf_xattn_fwd(F(sv, I.q), F(sv, I.kv), F(sv, I.kv) + inner, F(sv, I.out), F(sv, I.lse), d.B, d.heads, d.N, d.N,
@@ -185,10 +241,10 @@ static int instance_fwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
                                    nullptr, nullptr, stream));
     if (w.mask_g)
         TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2,
-                                          F(sv, I.m2), F(sv, I.r2), F(sv, I.f), F(sv, I.h), w.mask_g, stream));
+                                          F(sv, I.m2), F(sv, I.r2), f_out, F(sv, I.h), w.mask_g, stream));
     else
         TMF_TRY(tmf_tok_linear_fwd(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2, F(sv, I.m2),
-                                   F(sv, I.r2), F(sv, I.f), F(sv, I.h), stream));
+                                   F(sv, I.r2), f_out, F(sv, I.h), stream));
     if (w.mask_f)
         TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f,
                                           nullptr, nullptr, nullptr, nullptr, w.mask_f, stream));
@@ -196,7 +252,7 @@ static int instance_fwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
         TMF_TRY(tmf_tok_linear_fwd(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f, nullptr,
                                    nullptr, nullptr, nullptr, stream));
     // block-final LayerNorm with the caller's "+ tokens" (networks.py:274-275) folded into the same pass
-    TMF_TRY(tmf_layernorm_fwd(F(sv, I.x2), w.lnf_g, w.lnf_b, x, F(sv, I.y), F(sv, I.mf), F(sv, I.rf), R, dim, w.epsf, stream));
+    TMF_TRY(tmf_layernorm_fwd(F(sv, I.x2), w.lnf_g, w.lnf_b, x, y_out, F(sv, I.mf), F(sv, I.rf), R, dim, w.epsf, stream));
     return TMF_OK;
 }
 
@@ -237,7 +293,7 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
             tmf_xf_fwd_io io = {};
             io.x = pet_tok; io.pkv_next = F(base, I.pkf) + tmf_xf_pack_kv_offset();
             io.KRn = F(base, I.KR); io.KCn = F(base, I.KC); io.VRn = F(base, I.VR); io.VCn = F(base, I.VC);
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, nullptr, &io, scale, 1, d->heads == 8, s));
+            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, nullptr, &io, scale, 1, d->heads == 8, 0, s));
         }
         for (int i = 0; i < n_inst; ++i) {
             char* sv = base + (size_t)i * I.total;
@@ -253,7 +309,7 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
                 io.pkv_next = F(sn, I.pkf) + tmf_xf_pack_kv_offset();
                 io.KRn = F(sn, I.KR); io.KCn = F(sn, I.KC); io.VRn = F(sn, I.VR); io.VCn = F(sn, I.VC);
             }
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, &inst[i], &io, scale, 0, d->heads == 8, s));
+            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, &inst[i], &io, scale, 0, d->heads == 8, 0, s));
             if (i & 1) q = F(sv, I.y); else m = F(sv, I.y);
         }
         return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + p.off_arg), d->B, d->N, d->dim, stream);
@@ -267,6 +323,62 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
         q = F(sp, p.I.y);
     }
     return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + p.off_arg), d->B, d->N, d->dim, stream);
+}
+
+// Forward only (no_grad evaluation: val_step, kfold_train_adversarial.py:144-161; the test run after training, :229-250):
+// the launches of tmf_fusion_train_fwd with nothing kept.  Fused geometry: the forward-only instances of xf_fwd_kernel
+// and a forward-only weight pack; otherwise instance_fwd into one reused slab.
+extern "C" int tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
+                                    const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes, float* cls,
+                                    void* stream) {
+    TMF_TRY(check_desc("tmf_fusion_infer_fwd", d));
+    TMF_REQUIRE_PTR(mri_tok); TMF_REQUIRE_PTR(pet_tok); TMF_REQUIRE_PTR(workspace); TMF_REQUIRE_PTR(cls);
+    TMF_REQUIRE(d->depth == 0 || inst != nullptr, TMF_E_NULL, "tmf_fusion_infer_fwd: argument 'inst' is NULL");
+    TMF_REQUIRE_ALIGNED(mri_tok); TMF_REQUIRE_ALIGNED(pet_tok); TMF_REQUIRE_ALIGNED(workspace);
+    const InferPlan ip = make_infer_plan(*d);
+    const Plan& p = ip.p;
+    TMF_REQUIRE(workspace_bytes >= ip.bytes, TMF_E_WORKSPACE, "tmf_fusion_infer_fwd: workspace %zu B < required %zu B",
+                workspace_bytes, ip.bytes);
+    TMF_TRY(check_params("tmf_fusion_infer_fwd", inst, 2 * d->depth));
+    char* base = (char*)workspace;
+    const float* m = mri_tok;
+    const float* q = pet_tok;
+    const int n_inst = 2 * d->depth;
+    if (p.fused && d->depth > 0) {
+        const float scale = 1.0f / sqrtf((float)d->dim_head);
+        hipStream_t s = (hipStream_t)stream;
+        const size_t pk_stride = up256((size_t)tmf_xf_pack_floats() * 4);
+        float* pf[2 * TMF_FUSION_MAX_DEPTH];
+        for (int i = 0; i < n_inst; ++i) pf[i] = F(base, ip.pk + (size_t)i * pk_stride);
+        TMF_TRY(tmf_xf_launch_pack(n_inst, inst, pf, nullptr, s));
+        {   // K | V of the first instance's context (the pet tokens)
+            tmf_xf_fwd_io io = {};
+            io.x = pet_tok; io.pkv_next = pf[0] + tmf_xf_pack_kv_offset();
+            io.KRn = F(base, ip.KR[0]); io.VCn = F(base, ip.VC[0]);
+            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, nullptr, &io, scale, 1, d->heads == 8, 1, s));
+        }
+        for (int i = 0; i < n_inst; ++i) {
+            tmf_xf_fwd_io io = {};
+            io.x = (i & 1) ? q : m;
+            io.KR = F(base, ip.KR[i & 1]); io.VC = F(base, ip.VC[i & 1]); io.pk = pf[i];
+            io.mask_o = inst[i].mask_o; io.mask_g = inst[i].mask_g; io.mask_f = inst[i].mask_f;
+            io.y = F(base, ip.tok[i & 1][0]);
+            if (i + 1 < n_inst) {           // this output is the next instance's context
+                io.pkv_next = pf[i + 1] + tmf_xf_pack_kv_offset();
+                io.KRn = F(base, ip.KR[(i + 1) & 1]); io.VCn = F(base, ip.VC[(i + 1) & 1]);
+            }
+            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, &inst[i], &io, scale, 0, d->heads == 8, 1, s));
+            if (i & 1) q = io.y; else m = io.y;
+        }
+        return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + ip.arg), d->B, d->N, d->dim, stream);
+    }
+    for (int i = 0; i < n_inst; ++i) {
+        // mri <- T(mri | pet) + mri, then pet <- T(pet | NEW mri) + pet; the output buffer of a stream alternates per layer
+        float* y = F(base, ip.tok[i & 1][(i >> 1) & 1]);
+        TMF_TRY(instance_fwd(*d, p, inst[i], (i & 1) ? q : m, (i & 1) ? m : q, base + ip.slab, stream, y));
+        if (i & 1) q = y; else m = y;
+    }
+    return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + ip.arg), d->B, d->N, d->dim, stream);
 }
 
 // Backward of one instance.  dy = gradient w.r.t. its output y.  Writes

@@ -151,17 +151,23 @@ __device__ __forceinline__ void store_frag_head(float* __restrict__ XR, float* _
     for (int r = 0; r < 4; ++r)             // row fragment: features 2 m, 2 m + 1 of token 4 kb + r
         *reinterpret_cast<f32x2*>(dst + r * 4) = f32x2{acc[0][r], acc[1][r]};
 }
-// Producer side, the TPW = 4 to_kv GEMM: wave w holds features 64 w + 4 m + u of [K | V]: waves 0, 1 -> K, 2, 3 -> V
+// Producer side, the TPW = 4 to_kv GEMM: wave w holds features 64 w + 4 m + u of [K | V]: waves 0, 1 -> K, 2, 3 -> V.
+// FWD_ONLY: only what the forward reads — K's row fragments, V's column fragments (KC / VR serve dK / dV: not touched).
+template <bool FWD_ONLY = false>
 __device__ __forceinline__ void store_frag_kv(float* __restrict__ KR, float* __restrict__ KC, float* __restrict__ VR,
                                               float* __restrict__ VC, const f32x4 (&acc)[4], int b, int w, int tile, int T, int m, int kb) {
     float* XR = w < 2 ? KR : VR;
     float* XC = w < 2 ? KC : VC;
     const int h = 2 * (w & 1) + (m >> 3), sd = (m & 7) >> 2;
+    if (!FWD_ONLY || w >= 2) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) st4(XC + frag_c(b, h, sd, tile, T) + (kb * 16 + 4 * (m & 3) + u) * 4, acc[u]);
-    float* dst = XR + frag_r(b, h, tile, sd, T) + ((m & 3) * 16 + 4 * kb) * 4;
+        for (int u = 0; u < 4; ++u) st4(XC + frag_c(b, h, sd, tile, T) + (kb * 16 + 4 * (m & 3) + u) * 4, acc[u]);
+    }
+    if (!FWD_ONLY || w < 2) {
+        float* dst = XR + frag_r(b, h, tile, sd, T) + ((m & 3) * 16 + 4 * kb) * 4;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) st4(dst + r * 4, f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]});
+        for (int r = 0; r < 4; ++r) st4(dst + r * 4, f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]});
+    }
 }
 
 // Workgroup id -> (batch element, tile).  The grid is 1-D, 8 * ns workgroups with ns = tiles * ceil(B / 8): workgroup id
@@ -258,7 +264,10 @@ __device__ __forceinline__ f32x4 ln_row(const f32x4 v, const float* __restrict__
 // H2 (round 6): EIGHT heads of 16 features (train_adversarial.py:30-31) — a wave owns the two heads 2 wave, 2 wave + 1, which are
 // exactly the two 16-feature blocks s = 0, 1 of its 32 features: the fragment panels are the same memory (head' = 2 h + s), only
 // the contractions change (a head's scores sum ONE block, its output is ONE dt tile), lse / delta are [B][8][Npad].
-template <int MT, bool EXACT, bool H2>
+// INFER (tmf_fusion_infer_fwd): the same chain, the same arithmetic in the same order, and of the stores only y and the
+// next context's KR / VC — nothing is kept for a backward (a, QR, QC, out, lse, x1, f, h, g, x2, the six LayerNorm
+// statistics, KCn, VRn: those pointers are NULL).  A template parameter: the training instances carry no test for it.
+template <int MT, bool EXACT, bool H2, bool INFER = false>
 __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;                       // input rows
@@ -312,7 +321,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
             f32x4 a = ln_row(v, p.ln1_g, p.ln1_b, p.eps1, li, mu, rs);
             if (!ok) a = f32x4{0.f, 0.f, 0.f, 0.f};
             st4(As + row * XP + li * 4, a);
-            if (ok) {
+            if (!INFER && ok) {
                 st4(p.a + gr * XD + li * 4, a);
                 if (li == 0) { p.m1[gr] = mu; p.r1[gr] = rs; }
             }
@@ -354,7 +363,8 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 *reinterpret_cast<f32x2*>(Qs + (4 * kb + r) * XP + c0) = f32x2{acc[0][r], acc[1][r]};
-            store_frag_head(p.QR, p.QC, acc, bz, wave, tile, p.tiles, m, kb);     // rows past nv are exact zeros (their A rows are)
+            if constexpr (!INFER)
+                store_frag_head(p.QR, p.QC, acc, bz, wave, tile, p.tiles, m, kb);     // rows past nv are exact zeros (their A rows are)
         }
         __syncthreads();
 
@@ -367,8 +377,18 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
 #pragma unroll
             for (int hs = 0; hs < 2; ++hs) {
                 f32x4 k1[RD], v1[RD];
-                auto load_k1 = [&](int t, f32x4& dst) { dst = ld4(Kb + t * 512 + hs * 256); };
-                auto load_v1 = [&](int t, f32x4& dst) { dst = ld4(Vt + (size_t)(hs * ntiles + t) * 256); };
+                const float *Kh = Kb, *Vh = Vt;
+                if constexpr (INFER) {
+                    // Without the out / lse stores between the two heads nothing keeps the second head's 2 MT panel
+                    // addresses (64-bit each, offsets beyond the instructions' immediate range) from being computed
+                    // ahead of the FIRST head's softmax, on top of its MT score tiles: +16 registers at MT = 32.  An
+                    // offset the compiler cannot see through (zero) ties them to their own head.
+                    int z = 0;
+                    asm volatile("" : "+s"(z));
+                    Kh += z; Vh += z;
+                }
+                auto load_k1 = [&](int t, f32x4& dst) { dst = ld4(Kh + t * 512 + hs * 256); };
+                auto load_v1 = [&](int t, f32x4& dst) { dst = ld4(Vh + (size_t)(hs * ntiles + t) * 256); };
 #pragma unroll
                 for (int t = 0; t < RD - 1; ++t) {
                     k1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -442,8 +462,10 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                 const f32x4 w4 = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
                 const int cc = XDH * h + 16 * hs + 4 * kb;
                 st4(Os + m * XP + cc, w4);
-                if (m < nv) st4(p.out + (row0 + m) * XD + cc, w4);
-                if (kb == 0) p.lse[((size_t)bz * (2 * XH) + 2 * h + hs) * Npad + t0 + m] = m < nv ? mx + log2f(l) : INFINITY;
+                if constexpr (!INFER) {
+                    if (m < nv) st4(p.out + (row0 + m) * XD + cc, w4);
+                    if (kb == 0) p.lse[((size_t)bz * (2 * XH) + 2 * h + hs) * Npad + t0 + m] = m < nv ? mx + log2f(l) : INFINITY;
+                }
             }
         } else {
             const float c = p.scale * XLOG2E;
@@ -529,9 +551,9 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                 const f32x4 w4 = {o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv};
                 const int cc = XDH * h + 16 * dt + 4 * kb;
                 st4(Os + m * XP + cc, w4);
-                if (m < nv) st4(p.out + (row0 + m) * XD + cc, w4);
+                if (!INFER && m < nv) st4(p.out + (row0 + m) * XD + cc, w4);
             }
-            if (kb == 0) p.lse[((size_t)bz * XH + h) * Npad + t0 + m] = m < nv ? mx + log2f(l) : INFINITY;
+            if (!INFER && kb == 0) p.lse[((size_t)bz * XH + h) * Npad + t0 + m] = m < nv ? mx + log2f(l) : INFINITY;
         }
         __syncthreads();
 
@@ -557,7 +579,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                 }
                 v[0] += xr[0]; v[1] += xr[1];
                 *reinterpret_cast<f32x2*>(X1s + row * XP + c0) = v;
-                if (ok) *reinterpret_cast<f32x2*>(p.x1 + (row0 + row) * XD + c0) = v;
+                if (!INFER && ok) *reinterpret_cast<f32x2*>(p.x1 + (row0 + row) * XD + c0) = v;
             }
         }
         __syncthreads();
@@ -574,7 +596,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
             f32x4 f = ln_row(v, p.ln2_g, p.ln2_b, p.eps2, li, mu, rs);
             if (!ok) f = f32x4{0.f, 0.f, 0.f, 0.f};
             st4(As + row * XP + li * 4, f);
-            if (ok) {
+            if (!INFER && ok) {
                 st4(p.f + gr * XD + li * 4, f);
                 if (li == 0) { p.m2[gr] = mu; p.r2[gr] = rs; }
             }
@@ -606,7 +628,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                     }
                     if (!ok) gv = f32x4{0.f, 0.f, 0.f, 0.f};
                     st4(Gs + row * XGP + c0, gv);
-                    if (ok) {
+                    if (!INFER && ok) {
                         st4(p.h + (row0 + row) * XMLP + c0, hv);
                         st4(p.g + (row0 + row) * XMLP + c0, gv);
                     }
@@ -636,7 +658,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
                 }
                 v[0] += xr[0]; v[1] += xr[1];
                 *reinterpret_cast<f32x2*>(Ys + row * XP + c0) = v;
-                if (ok) *reinterpret_cast<f32x2*>(p.x2 + (row0 + row) * XD + c0) = v;
+                if (!INFER && ok) *reinterpret_cast<f32x2*>(p.x2 + (row0 + row) * XD + c0) = v;
             }
         }
         __syncthreads();
@@ -657,7 +679,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
             st4(Ys + row * XP + li * 4, y);             // the same lanes read and write this row
             if (ok) {
                 st4(p.y + gr * XD + li * 4, y);
-                if (li == 0) { p.mf[gr] = mu; p.rf[gr] = rs; }
+                if (!INFER && li == 0) { p.mf[gr] = mu; p.rf[gr] = rs; }
             }
         }
         __syncthreads();
@@ -671,7 +693,7 @@ __global__ __launch_bounds__(XTHR, 1) void xf_fwd_kernel(const XfFwdArgs p) {
         f32x4 acc[4];
         zero_acc<4>(acc);
         gkv.run(acc, Ys, XP, lane);
-        store_frag_kv(p.KRn, p.KCn, p.VRn, p.VCn, acc, bz, wave, tile, p.tiles, m, kb);       // rows past nv: zeros
+        store_frag_kv<INFER>(p.KRn, p.KCn, p.VRn, p.VCn, acc, bz, wave, tile, p.tiles, m, kb);       // rows past nv: zeros
     }
     XF_STAMP(11);
 }
@@ -1335,29 +1357,32 @@ enum { XF_BK_2 = 0, XF_BK_1 = XMLP * XD, XF_BK_O = 2 * XMLP * XD, XF_BK_Q = 2 * 
 int tmf_xf_pack_floats(void) { return XF_PACK_FLOATS; }
 int tmf_xf_pack_kv_offset(void) { return XF_PK_KV; }
 
-// Re-pack the weights of n_inst instances: pk_fwd[i] / pk_bwd[i] = XF_PACK_FLOATS floats each.
+// Re-pack the weights of n_inst instances: pk_fwd[i] / pk_bwd[i] = XF_PACK_FLOATS floats each.  pk_bwd == NULL (the
+// forward-only entry): the five forward packs of an instance alone — half the table, half the grid, half the bytes.
 int tmf_xf_launch_pack(int n_inst, const tmf_xformer_params* inst, float* const* pk_fwd, float* const* pk_bwd, hipStream_t s) {
-    for (int i0 = 0; i0 < n_inst; i0 += XF_PACK_MAX / 10) {
-        const int ni = (n_inst - i0) < XF_PACK_MAX / 10 ? (n_inst - i0) : XF_PACK_MAX / 10;
+    const int per = pk_bwd != nullptr ? 10 : 5;                 // table entries per instance
+    for (int i0 = 0; i0 < n_inst; i0 += XF_PACK_MAX / per) {
+        const int ni = (n_inst - i0) < XF_PACK_MAX / per ? (n_inst - i0) : XF_PACK_MAX / per;
         XfPackArgs a = {};
         for (int k = 0; k < ni; ++k) {
             const tmf_xformer_params& w = inst[i0 + k];
             float* f = pk_fwd[i0 + k];
-            float* b = pk_bwd[i0 + k];
-            XfPackDesc* d = a.d + 10 * k;
+            XfPackDesc* d = a.d + per * k;
             d[0] = {w.wq, f + XF_PK_Q, XD, XD, 2, 8, 0};
             d[1] = {w.wo, f + XF_PK_O, XD, XD, 2, 8, 0};
             d[2] = {w.w1, f + XF_PK_1, XMLP, XD, 8, 8, 0};
             d[3] = {w.w2, f + XF_PK_2, XD, XMLP, 2, 32, 0};
             d[4] = {w.wkv, f + XF_PK_KV, 2 * XD, XD, 4, 8, 0};
+            if (pk_bwd == nullptr) continue;
+            float* b = pk_bwd[i0 + k];
             d[5] = {w.w2, b + XF_BK_2, XMLP, XD, 8, 8, 1};             // dg = dx2 W2:  W2 [dim][mlp]
             d[6] = {w.w1, b + XF_BK_1, XD, XMLP, 2, 32, 1};            // df = dh W1:   W1 [mlp][dim]
             d[7] = {w.wo, b + XF_BK_O, XD, XD, 2, 8, 1};               // dout = dx1 Wo
             d[8] = {w.wq, b + XF_BK_Q, XD, XD, 2, 8, 1};               // da = dq Wq
             d[9] = {w.wkv, b + XF_BK_KV, XD, 2 * XD, 2, 16, 1};        // dctx = dkv Wkv: Wkv [2 inner][dim]
         }
-        hipLaunchKernelGGL(xf_pack_kernel, dim3(XMLP * XD / 4 / 256, 10 * ni), dim3(256), 0, s, a);
-        int rc = tmf_launch_result("tmf_fusion_train_fwd(weight packs)");
+        hipLaunchKernelGGL(xf_pack_kernel, dim3(XMLP * XD / 4 / 256, per * ni), dim3(256), 0, s, a);
+        int rc = tmf_launch_result(pk_bwd != nullptr ? "tmf_fusion_train_fwd(weight packs)" : "tmf_fusion_infer_fwd(weight packs)");
         if (rc) return rc;
     }
     return TMF_OK;
@@ -1368,8 +1393,9 @@ struct tmf_xf_fwd_io {
     float *a, *QR, *QC, *out, *lse, *x1, *f, *h, *g, *x2, *y, *m1, *r1, *m2, *r2, *mf, *rf, *KRn, *KCn, *VRn, *VCn;
 };
 
+// infer != 0: the forward-only instances (the io's saved-for-backward pointers, KCn and VRn are not looked at)
 int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fwd_io* io, float scale, int only_kv, int h2,
-                      hipStream_t s) {
+                      int infer, hipStream_t s) {
     XfFwdArgs a = {};
     a.x = io->x; a.KR = io->KR; a.VC = io->VC; a.pkv_next = io->pkv_next;
     a.mask_o = io->mask_o; a.mask_g = io->mask_g; a.mask_f = io->mask_f;
@@ -1388,10 +1414,12 @@ int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fw
     const dim3 grid(8 * a.tiles * ((B + 7) / 8)), block(XTHR);
     const int mt = a.Npad / 16;
     int rc;
+    const char* what = infer ? "tmf_fusion_infer_fwd(fused)" : "tmf_fusion_train_fwd(fused)";
 #define XF_LAUNCH(MT, EX)                                                                     \
     {                                                                                         \
-        auto kf = h2 ? xf_fwd_kernel<MT, EX, true> : xf_fwd_kernel<MT, EX, false>;            \
-        if ((rc = tmf_allow_lds(kf, XF_FWD_LDS, "tmf_fusion_train_fwd(fused)"))) return rc;   \
+        auto kf = infer ? (h2 ? xf_fwd_kernel<MT, EX, true, true> : xf_fwd_kernel<MT, EX, false, true>)      \
+                        : (h2 ? xf_fwd_kernel<MT, EX, true> : xf_fwd_kernel<MT, EX, false>);  \
+        if ((rc = tmf_allow_lds(kf, XF_FWD_LDS, what))) return rc;                            \
         hipLaunchKernelGGL(kf, grid, block, XF_FWD_LDS, s, a);                                \
     }
     // exact instances for the token counts of the benchmark volumes (96^3 -> 216, 91x109x91 -> 150, 128^3 -> 512)
@@ -1402,7 +1430,7 @@ int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fw
     else if (mt <= 16) XF_LAUNCH(16, false)
     else XF_LAUNCH(32, false)
 #undef XF_LAUNCH
-    return tmf_launch_result("tmf_fusion_train_fwd(fused)");
+    return tmf_launch_result(what);
 }
 
 struct tmf_xf_bwd_io {

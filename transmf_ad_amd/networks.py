@@ -301,6 +301,16 @@ class CrossTransformer_MOD_AVG(nn.Module):
         the whole fusion is one library call per pass (ops.FusionTrain), active Dropout as keep-masks."""
         if not (mri_tokens.is_cuda and torch.is_grad_enabled()) or len(self.layers) == 0:
             return False
+        return self._one_call_geometry_ok(mri_tokens)
+
+    def _infer_one_call_ok(self, mri_tokens):
+        """Grad mode off (val_step, the test run, bench.py --eval): the same conditions, and the whole fusion is ONE
+        forward-only library call that keeps nothing (ops.fusion_infer) — unless ops.FUSION_INFER_ONE_CALL is off."""
+        if not ops.fusion_infer_ok(mri_tokens) or len(self.layers) == 0:
+            return False
+        return self._one_call_geometry_ok(mri_tokens)
+
+    def _one_call_geometry_ok(self, mri_tokens):
         t0 = self.layers[0][0]
         a, f = t0.layers[0][0].fn, t0.layers[0][1].fn
         inner = a.to_q.out_features
@@ -322,7 +332,8 @@ class CrossTransformer_MOD_AVG(nn.Module):
 
     @device_guard
     def forward(self, mri_tokens, pet_tokens):
-        if self._one_call_ok(mri_tokens):
+        train_call = self._one_call_ok(mri_tokens)
+        if train_call or (pet_tokens.shape == mri_tokens.shape and self._infer_one_call_ok(mri_tokens)):
             params, eps, drops = [], [], []
             for pair in self.layers:
                 for tr in pair:
@@ -337,6 +348,8 @@ class CrossTransformer_MOD_AVG(nn.Module):
             f0 = self.layers[0][0].layers[0][1].fn
             cfg = (a0.heads, a0.to_q.out_features // a0.heads, f0.net[0].out_features, len(self.layers), tuple(eps),
                    tuple(drops) if any(tr._dropout_active() for pair in self.layers for tr in pair) else None)
+            if not train_call:
+                return ops.fusion_infer(mri_tokens, pet_tokens, cfg, params)
             return ops.FusionTrain.apply(mri_tokens, pet_tokens, cfg, *params)
         for mri_enc, pet_enc in self.layers:
             # (Transformer.forward can fold this "+ tokens" into its last LayerNorm pass via residual=; it is left

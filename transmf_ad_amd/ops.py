@@ -1174,6 +1174,60 @@ def fusion_takes_masks(dim, inner, mlp, dim_head):
     return dim in TOKEN_GEMM_DIMS and inner % 64 == 0 and mlp % 64 == 0 and dim_head in (8, 16, 32, 64)
 
 
+def _fusion_call_setup(mri, pet, cfg, params):
+    """What both fusion entries take: checked tokens, the descriptor, the per-instance parameter table (tmf_xformer_params,
+    pointers of `params` in _lib.XFORMER_PTRS order) and this call's Dropout keep-masks (kept alive by the returned list)."""
+    mri, pet = _chk(mri, "mri_tokens"), _chk(pet, "pet_tokens")
+    heads, dim_head, mlp, depth, eps = cfg[:5]
+    drops = cfg[5] if len(cfg) > 5 else None      # per instance the three nn.Dropout modules (to_out, GELU, Linear 2)
+    B, N, dim = mri.shape
+    if pet.shape != mri.shape:
+        raise _lib.TmfError(f"token shapes differ: {tuple(mri.shape)} vs {tuple(pet.shape)}")
+    desc = _lib.FusionDesc(B=B, N=N, dim=dim, heads=heads, dim_head=dim_head, mlp=mlp, depth=depth,
+                           flags=0 if FUSION_FUSED_KERNELS else _lib.FUSION_PER_OP)
+    inst = (_lib.XformerParams * (2 * depth))()
+    masks = []
+    for i in range(2 * depth):
+        for j, name in enumerate(_lib.XFORMER_PTRS):
+            t = params[14 * i + j]
+            if not (t.is_cuda and t.dtype == _f32 and t.is_contiguous()):
+                raise _lib.TmfError(f"Transformer instance {i}: {name} must be a contiguous float32 HIP tensor")
+            setattr(inst[i], name, t.data_ptr())
+        inst[i].eps1, inst[i].eps2, inst[i].epsf = eps[i]
+    if drops is not None:                    # every keep-mask of the step in one draw per distinct p
+        req = [(drop, (B * N, width)) for i in range(2 * depth) for drop, width in zip(drops[i], (dim, mlp, dim))]
+        for j, mk in enumerate(dropout_keep_masks(req, mri.device)):
+            if mk is not None:
+                masks.append(mk)
+                setattr(inst[j // 3], ("mask_o", "mask_g", "mask_f")[j % 3], mk.data_ptr())
+    return mri, pet, desc, inst, masks
+
+
+FUSION_INFER_ONE_CALL = os.environ.get("TMF_FUSION_INFER_C", "1") != "0"
+
+
+def fusion_infer_ok(mri_tokens):
+    """The part of the forward-only route's predicate that does not depend on the module (networks.CrossTransformer_MOD_AVG
+    adds its own geometry / hook checks): device tokens, grad mode off, the switch on."""
+    return FUSION_INFER_ONE_CALL and mri_tokens.is_cuda and not torch.is_grad_enabled()
+
+
+def fusion_infer(mri_tok, pet_tok, cfg, params):
+    """CrossTransformer_MOD_AVG's forward under no_grad as ONE library call that keeps nothing (tmf_fusion_infer_fwd,
+    csrc/fusion_path.hip): cfg and params as FusionTrain.forward takes them -> cls (B, 4*dim), bit-identical to
+    FusionTrain's.  No autograd."""
+    import ctypes as C
+    mri, pet, desc, inst, masks = _fusion_call_setup(mri_tok, pet_tok, cfg, params)
+    nws = _lib.query("tmf_fusion_infer_workspace_bytes", C.byref(desc))
+    if nws == 0:
+        raise _lib.TmfError("tmf_fusion_infer_workspace_bytes: " + (_lib.load().tmf_last_error_string() or b"").decode())
+    ws = torch.empty(nws, device=mri.device, dtype=torch.uint8)
+    cls = torch.empty((mri.shape[0], 4 * mri.shape[2]), device=mri.device, dtype=_f32)
+    _lib.call("tmf_fusion_infer_fwd", C.byref(desc), mri.data_ptr(), pet.data_ptr(), inst, ws.data_ptr(), nws,
+              cls.data_ptr(), _stream())
+    return cls
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
@@ -1182,29 +1236,8 @@ class FusionTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mri, pet, cfg, *params):
         import ctypes as C
-        mri, pet = _chk(mri, "mri_tokens"), _chk(pet, "pet_tokens")
-        heads, dim_head, mlp, depth, eps = cfg[:5]
-        drops = cfg[5] if len(cfg) > 5 else None      # per instance the three nn.Dropout modules (to_out, GELU, Linear 2)
-        B, N, dim = mri.shape
-        if pet.shape != mri.shape:
-            raise _lib.TmfError(f"token shapes differ: {tuple(mri.shape)} vs {tuple(pet.shape)}")
-        desc = _lib.FusionDesc(B=B, N=N, dim=dim, heads=heads, dim_head=dim_head, mlp=mlp, depth=depth,
-                               flags=0 if FUSION_FUSED_KERNELS else _lib.FUSION_PER_OP)
-        inst = (_lib.XformerParams * (2 * depth))()
-        masks = []
-        for i in range(2 * depth):
-            for j, name in enumerate(_lib.XFORMER_PTRS):
-                t = params[14 * i + j]
-                if not (t.is_cuda and t.dtype == _f32 and t.is_contiguous()):
-                    raise _lib.TmfError(f"Transformer instance {i}: {name} must be a contiguous float32 HIP tensor")
-                setattr(inst[i], name, t.data_ptr())
-            inst[i].eps1, inst[i].eps2, inst[i].epsf = eps[i]
-        if drops is not None:                    # every keep-mask of the step in one draw per distinct p
-            req = [(drop, (B * N, width)) for i in range(2 * depth) for drop, width in zip(drops[i], (dim, mlp, dim))]
-            for j, mk in enumerate(dropout_keep_masks(req, mri.device)):
-                if mk is not None:
-                    masks.append(mk)
-                    setattr(inst[j // 3], ("mask_o", "mask_g", "mask_f")[j % 3], mk.data_ptr())
+        mri, pet, desc, inst, masks = _fusion_call_setup(mri, pet, cfg, params)
+        B, _N, dim = mri.shape
         nsaved = _lib.query("tmf_fusion_saved_bytes", C.byref(desc))
         if nsaved == 0:
             raise _lib.TmfError("tmf_fusion_saved_bytes: " + (_lib.load().tmf_last_error_string() or b"").decode())
