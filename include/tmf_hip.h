@@ -389,11 +389,14 @@ int tmf_xattn_bwd_cat(const float* q, const float* k1, const float* v1, const fl
 int tmf_layernorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
                       float* mean, float* rstd, int rows, int dim, float eps, void* stream);
 int tmf_layernorm_bwd_blocks(int rows, int dim);
-/* partial: [nblk][2][dim] (dgamma, dbeta partials; reduce with tmf_colsum_finalize, ncol = 2*dim). */
+/* partial: [nblk][2][dim] (dgamma, dbeta partials; reduce with tmf_colsum_finalize, ncol = 2*dim).
+ * Shares its implementation with tmf_layernorm_bwd_masked below: this entry is that one without a mask. */
 int tmf_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd,
                       const float* dy, float* dx, float* partial, int rows, int dim, void* stream);
 /* The same, and also dx_masked = dx * mask (mask [rows][dim]: a Dropout keep-mask already scaled by 1 / (1 - p)) in the
- * same pass: the block-final LayerNorm's input gradient and its m_f-masked copy (networks.py:133). */
+ * same pass: the block-final LayerNorm's input gradient and its m_f-masked copy (networks.py:133).  One implementation
+ * serves both entries (same checks, same launch geometry); the _masked form adds: mask and dx_masked, both required,
+ * and the <VEC, true> kernel instances. */
 int tmf_layernorm_bwd_masked(const float* x, const float* gamma, const float* mean, const float* rstd,
                              const float* dy, float* dx, float* partial, int rows, int dim,
                              const float* mask, float* dx_masked, void* stream);
@@ -418,6 +421,8 @@ int tmf_mask_mul(const float* x, const float* mask, float* y, long n, void* stre
  *   otherwise E(v) = v + add1.   add1 / add2 [R][K] may be NULL.
  *   bias_partial != NULL: column sums of the block's dy rows -> bias_partial[blk * partial_stride + c], c < Nout.
  *   blk < tmf_tok_row_blocks(R); reduce the partials with tmf_colsum_finalize(partial, nblk, partial_stride, ..).
+ * tmf_tok_linear_fwd and tmf_tok_linear_bwd_input each share ONE implementation with their _masked (Dropout) form
+ * below: they are that implementation without a mask, and run the plain epilogue instances.
  * ---------------------------------------------------------------------------- */
 int tmf_tok_row_blocks(int R);
 int tmf_tok_linear_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y,
@@ -427,7 +432,11 @@ int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* dx, int R, 
                              const float* gelu_pre, const float* ln_x, const float* ln_mean, const float* ln_rstd,
                              const float* ln_gamma, const float* add1, const float* add2, float* ln_partial,
                              float* bias_partial, int partial_stride, void* stream);
-/* Dropout forms (networks.py:131,133,153), same shapes and checks; mask: a keep-mask already scaled by 1 / (1 - p), never NULL.
+/* Dropout forms (networks.py:131,133,153); mask: a keep-mask already scaled by 1 / (1 - p), never NULL.  Each is one
+ * implementation with its plain entry above: the same argument checks in the same order (messages carry the called entry's
+ * name), tiles and instance rule; the _masked form adds the mask, the *_MASK epilogue instances and, in backward, the rules
+ * below — the plain backward also takes neither epilogue (dx = dy . w + add1, add2 then refused) and ignores add1 / add2
+ * beside gelu_pre.
  * forward:  y = (..) . w^T + bias,  then  y = y * mask [+ residual]   or, gelu_pre != NULL,  y = GELU(gelu_pre) * mask
  *   (gelu_pre itself unmasked); mask [R][Nout].
  * backward (mask [R][K]): exactly one of

@@ -62,6 +62,12 @@ struct InstPlan {
 
 constexpr int WG_CHUNK = 30;    // weight-gradient problems per tmf_tok_wgrad_multi launch (6 instances)
 
+// The five weight gradients dW [N][K] of one instance, in the order every table here lists them: w2, w1, wo, wkv, wq
+void wgrad_shapes(int dim, int inner, int mlp, int* N, int* K) {
+    const int N5[5] = {dim, mlp, dim, 2 * inner, inner}, K5[5] = {mlp, dim, inner, dim, dim};
+    for (int j = 0; j < 5; ++j) { N[j] = N5[j]; K[j] = K5[j]; }
+}
+
 struct Plan {
     int R, inner, nblk, nblk_ln, stride;
     bool fused;                 // one launch per instance and direction (xformer_fused.hip)
@@ -102,7 +108,7 @@ Plan make_plan(const tmf_fusion_desc& d) {
     p.nblk_ln = tmf_layernorm_bwd_blocks(p.R, d.dim);
     p.stride = 6 * d.dim + d.mlp;
     o = 0;
-    const int N5[5] = {d.dim, d.mlp, d.dim, 2 * p.inner, p.inner}, K5[5] = {d.mlp, d.dim, p.inner, d.dim, d.dim};
+    int Nc[WG_CHUNK], Kc[WG_CHUNK];
     if (p.fused) {
         // per instance (kept until the one weight-gradient launch at the end): dx2, dh, dx1, dq, dkv, column-sum partials
         p.stride = tmf_xf_part_stride();
@@ -118,9 +124,7 @@ Plan make_plan(const tmf_fusion_desc& d) {
         int n_inst = 2 * d.depth;
         if (n_inst > WG_CHUNK / 5) n_inst = WG_CHUNK / 5;
         if (n_inst < 1) n_inst = 1;
-        int Nc[WG_CHUNK], Kc[WG_CHUNK];
-        for (int i = 0; i < n_inst; ++i)
-            for (int j = 0; j < 5; ++j) { Nc[5 * i + j] = N5[j]; Kc[5 * i + j] = K5[j]; }
+        for (int i = 0; i < n_inst; ++i) wgrad_shapes(d.dim, p.inner, d.mlp, Nc + 5 * i, Kc + 5 * i);
         p.ws_bytes = tmf_tok_wgrad_multi_workspace_bytes(5 * n_inst, Nc, Kc);
     } else {
         p.s_dx2 = take(R * dim); p.s_dh = take(R * mlp); p.s_dx1 = take(R * dim); p.s_dout = take(R * inner);
@@ -128,7 +132,8 @@ Plan make_plan(const tmf_fusion_desc& d) {
         p.s_part = take((size_t)p.nblk * p.stride); p.s_lnpart = take((size_t)p.nblk_ln * 2 * dim);
         p.s_DR = p.s_DC = p.s_delta = p.inst_stride = 0;
         for (int i = 0; i < 4; ++i) p.s_G[i] = take(R * dim);
-        p.ws_bytes = tmf_tok_wgrad_multi_workspace_bytes(5, N5, K5);
+        wgrad_shapes(d.dim, p.inner, d.mlp, Nc, Kc);
+        p.ws_bytes = tmf_tok_wgrad_multi_workspace_bytes(5, Nc, Kc);
     }
     if (p.ws_bytes < 16) p.ws_bytes = 16;
     p.s_ws = take(p.ws_bytes / 4 + 1);
@@ -233,24 +238,12 @@ static int instance_fwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
     TMF_TRY(tmf_xattn_fwd(F(sv, I.q), F(sv, I.kv), F(sv, I.kv) + inner, F(sv, I.out), F(sv, I.lse), d.B, d.heads, d.N, d.N,
                           d.dim_head, inner, 2 * inner, scale, stream));
     // Dropout (masks non-NULL): x1 = m_o (out Wo^T + bo) + x,  g = m_g GELU(h) with h unmasked,  x2 = m_f (g W2^T + b2) + x1
-    if (w.mask_o)
-        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr,
-                                          nullptr, nullptr, nullptr, w.mask_o, stream));
-    else
-        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr, nullptr,
-                                   nullptr, nullptr, stream));
-    if (w.mask_g)
-        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2,
-                                          F(sv, I.m2), F(sv, I.r2), f_out, F(sv, I.h), w.mask_g, stream));
-    else
-        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2, F(sv, I.m2),
-                                   F(sv, I.r2), f_out, F(sv, I.h), stream));
-    if (w.mask_f)
-        TMF_TRY(tmf_tok_linear_fwd_masked(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f,
-                                          nullptr, nullptr, nullptr, nullptr, w.mask_f, stream));
-    else
-        TMF_TRY(tmf_tok_linear_fwd(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f, nullptr,
-                                   nullptr, nullptr, nullptr, stream));
+    TMF_TRY(tmf_tok_linear_fwd_impl(F(sv, I.out), w.wo, w.bo, x, F(sv, I.x1), R, inner, dim, nullptr, nullptr, 0.f, nullptr, nullptr,
+                                   nullptr, nullptr, w.mask_o, stream));
+    TMF_TRY(tmf_tok_linear_fwd_impl(F(sv, I.x1), w.w1, w.b1, nullptr, F(sv, I.g), R, dim, mlp, w.ln2_g, w.ln2_b, w.eps2, F(sv, I.m2),
+                                   F(sv, I.r2), f_out, F(sv, I.h), w.mask_g, stream));
+    TMF_TRY(tmf_tok_linear_fwd_impl(F(sv, I.g), w.w2, w.b2, F(sv, I.x1), F(sv, I.x2), R, mlp, dim, nullptr, nullptr, 0.f, nullptr,
+                                   nullptr, nullptr, nullptr, w.mask_f, stream));
     // block-final LayerNorm with the caller's "+ tokens" (networks.py:274-275) folded into the same pass
     TMF_TRY(tmf_layernorm_fwd(F(sv, I.x2), w.lnf_g, w.lnf_b, x, y_out, F(sv, I.mf), F(sv, I.rf), R, dim, w.epsf, stream));
     return TMF_OK;
@@ -265,12 +258,59 @@ static int check_params(const char* fn, const tmf_xformer_params* w, int n) {
     return TMF_OK;
 }
 
+// Where one instance of the fused forward keeps its buffers.  out: what it writes (a field left NULL is not written: the
+// forward-only instances set y alone); KR .. VC: the panels of its context, written by the instance before it; pk, pkb: its
+// forward / backward weight packs.
+struct XfInst { tmf_xf_fwd_io out; float *KR, *KC, *VR, *VC, *pk, *pkb; };
+
+// The fused forward of both entries: pack, K | V of the first context, one launch per instance, pool.  at(i): instance i's XfInst
+template <class At>
+static int fused_fwd(const tmf_fusion_desc& d, const tmf_xformer_params* inst, const float* m, const float* q, At at, int infer,
+                     float* cls, int32_t* argmax, void* stream) {
+    const float scale = 1.0f / sqrtf((float)d.dim_head);
+    hipStream_t s = (hipStream_t)stream;
+    const int n_inst = 2 * d.depth;
+    XfInst b[2 * TMF_FUSION_MAX_DEPTH];
+    float* pf[2 * TMF_FUSION_MAX_DEPTH];
+    float* pb[2 * TMF_FUSION_MAX_DEPTH];
+    for (int i = 0; i < n_inst; ++i) { b[i] = at(i); pf[i] = b[i].pk; pb[i] = b[i].pkb; }
+    TMF_TRY(tmf_xf_launch_pack(n_inst, inst, pf, infer ? nullptr : pb, s));    // this step's weights in fragment order
+    for (int i = -1; i < n_inst; ++i) {               // pass -1 only makes K | V of the first context (the pet tokens)
+        const bool kv_only = i < 0;
+        tmf_xf_fwd_io io = {};
+        if (!kv_only) {
+            io = b[i].out;
+            io.KR = b[i].KR; io.VC = b[i].VC; io.pk = b[i].pk;
+            io.mask_o = inst[i].mask_o; io.mask_g = inst[i].mask_g; io.mask_f = inst[i].mask_f;
+        }
+        io.x = (kv_only || (i & 1)) ? q : m;
+        if (i + 1 < n_inst) {                         // what this pass writes is the next instance's context
+            const XfInst& n = b[i + 1];
+            io.pkv_next = n.pk + tmf_xf_pack_kv_offset();
+            io.KRn = n.KR; io.KCn = n.KC; io.VRn = n.VR; io.VCn = n.VC;
+        }
+        TMF_TRY(tmf_xf_launch_fwd(d.B, d.N, kv_only ? nullptr : &inst[i], &io, scale, kv_only, d.heads == 8, infer, s));
+        if (!kv_only) { if (i & 1) q = io.y; else m = io.y; }
+    }
+    return tmf_token_pool_fwd(m, q, cls, argmax, d.B, d.N, d.dim, stream);
+}
+
+// What both forward entries ask of their arguments before they plan.  ws: `saved` or `workspace`, named ws_name in the messages
+static int check_fwd_args(const char* fn, const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
+                          const tmf_xformer_params* inst, const void* ws, const char* ws_name, const float* cls) {
+    TMF_TRY(check_desc(fn, d));
+    TMF_REQUIRE_PTR_FN(fn, mri_tok); TMF_REQUIRE_PTR_FN(fn, pet_tok);
+    TMF_REQUIRE(ws != nullptr, TMF_E_NULL, "%s: argument '%s' is NULL", fn, ws_name);
+    TMF_REQUIRE_PTR_FN(fn, cls);
+    TMF_REQUIRE(d->depth == 0 || inst != nullptr, TMF_E_NULL, "%s: argument 'inst' is NULL", fn);
+    TMF_REQUIRE_ALIGNED_FN(fn, mri_tok); TMF_REQUIRE_ALIGNED_FN(fn, pet_tok);
+    TMF_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, TMF_E_ALIGN, "%s: argument '%s' is not 16-byte aligned", fn, ws_name);
+    return TMF_OK;
+}
+
 extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
                                     const tmf_xformer_params* inst, void* saved, size_t saved_bytes, float* cls, void* stream) {
-    TMF_TRY(check_desc("tmf_fusion_train_fwd", d));
-    TMF_REQUIRE_PTR(mri_tok); TMF_REQUIRE_PTR(pet_tok); TMF_REQUIRE_PTR(saved); TMF_REQUIRE_PTR(cls);
-    TMF_REQUIRE(d->depth == 0 || inst != nullptr, TMF_E_NULL, "tmf_fusion_train_fwd: argument 'inst' is NULL");
-    TMF_REQUIRE_ALIGNED(mri_tok); TMF_REQUIRE_ALIGNED(pet_tok); TMF_REQUIRE_ALIGNED(saved);
+    TMF_TRY(check_fwd_args(__func__, d, mri_tok, pet_tok, inst, saved, "saved", cls));
     const Plan p = make_plan(*d);
     TMF_REQUIRE(saved_bytes >= p.saved_bytes, TMF_E_WORKSPACE, "tmf_fusion_train_fwd: saved workspace %zu B < required %zu B",
                 saved_bytes, p.saved_bytes);
@@ -279,40 +319,18 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
     const float* m = mri_tok;
     const float* q = pet_tok;
     if (p.fused && d->depth > 0) {
-        const float scale = 1.0f / sqrtf((float)d->dim_head);
-        hipStream_t s = (hipStream_t)stream;
-        const int n_inst = 2 * d->depth;
         const InstPlan& I = p.I;
-        {   // this step's weights in fragment order (forward and backward forms)
-            float* pf[2 * TMF_FUSION_MAX_DEPTH];
-            float* pb[2 * TMF_FUSION_MAX_DEPTH];
-            for (int i = 0; i < n_inst; ++i) { pf[i] = F(base + (size_t)i * I.total, I.pkf); pb[i] = F(base + (size_t)i * I.total, I.pkb); }
-            TMF_TRY(tmf_xf_launch_pack(n_inst, inst, pf, pb, s));
-        }
-        {   // K | V of the first instance's context (the pet tokens)
-            tmf_xf_fwd_io io = {};
-            io.x = pet_tok; io.pkv_next = F(base, I.pkf) + tmf_xf_pack_kv_offset();
-            io.KRn = F(base, I.KR); io.KCn = F(base, I.KC); io.VRn = F(base, I.VR); io.VCn = F(base, I.VC);
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, nullptr, &io, scale, 1, d->heads == 8, 0, s));
-        }
-        for (int i = 0; i < n_inst; ++i) {
+        auto at = [&](int i) {                      // everything of an instance lives in its slab
             char* sv = base + (size_t)i * I.total;
-            tmf_xf_fwd_io io = {};
-            io.x = (i & 1) ? q : m;
-            io.KR = F(sv, I.KR); io.VC = F(sv, I.VC); io.pk = F(sv, I.pkf);
-            io.mask_o = inst[i].mask_o; io.mask_g = inst[i].mask_g; io.mask_f = inst[i].mask_f;
+            XfInst b = {};
+            tmf_xf_fwd_io& io = b.out;
             io.a = F(sv, I.a); io.QR = F(sv, I.QR); io.QC = F(sv, I.QC); io.out = F(sv, I.out); io.lse = F(sv, I.lse);
             io.x1 = F(sv, I.x1); io.f = F(sv, I.f); io.h = F(sv, I.h); io.g = F(sv, I.g); io.x2 = F(sv, I.x2); io.y = F(sv, I.y);
             io.m1 = F(sv, I.m1); io.r1 = F(sv, I.r1); io.m2 = F(sv, I.m2); io.r2 = F(sv, I.r2); io.mf = F(sv, I.mf); io.rf = F(sv, I.rf);
-            if (i + 1 < n_inst) {           // this output is the next instance's context
-                char* sn = sv + I.total;
-                io.pkv_next = F(sn, I.pkf) + tmf_xf_pack_kv_offset();
-                io.KRn = F(sn, I.KR); io.KCn = F(sn, I.KC); io.VRn = F(sn, I.VR); io.VCn = F(sn, I.VC);
-            }
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, &inst[i], &io, scale, 0, d->heads == 8, 0, s));
-            if (i & 1) q = F(sv, I.y); else m = F(sv, I.y);
-        }
-        return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + p.off_arg), d->B, d->N, d->dim, stream);
+            b.KR = F(sv, I.KR); b.KC = F(sv, I.KC); b.VR = F(sv, I.VR); b.VC = F(sv, I.VC); b.pk = F(sv, I.pkf); b.pkb = F(sv, I.pkb);
+            return b;
+        };
+        return fused_fwd(*d, inst, m, q, at, 0, cls, (int32_t*)(base + p.off_arg), stream);
     }
     for (int l = 0; l < d->depth; ++l) {
         char* sm = base + (size_t)(2 * l) * p.I.total;
@@ -331,10 +349,7 @@ extern "C" int tmf_fusion_train_fwd(const tmf_fusion_desc* d, const float* mri_t
 extern "C" int tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
                                     const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes, float* cls,
                                     void* stream) {
-    TMF_TRY(check_desc("tmf_fusion_infer_fwd", d));
-    TMF_REQUIRE_PTR(mri_tok); TMF_REQUIRE_PTR(pet_tok); TMF_REQUIRE_PTR(workspace); TMF_REQUIRE_PTR(cls);
-    TMF_REQUIRE(d->depth == 0 || inst != nullptr, TMF_E_NULL, "tmf_fusion_infer_fwd: argument 'inst' is NULL");
-    TMF_REQUIRE_ALIGNED(mri_tok); TMF_REQUIRE_ALIGNED(pet_tok); TMF_REQUIRE_ALIGNED(workspace);
+    TMF_TRY(check_fwd_args(__func__, d, mri_tok, pet_tok, inst, workspace, "workspace", cls));
     const InferPlan ip = make_infer_plan(*d);
     const Plan& p = ip.p;
     TMF_REQUIRE(workspace_bytes >= ip.bytes, TMF_E_WORKSPACE, "tmf_fusion_infer_fwd: workspace %zu B < required %zu B",
@@ -345,32 +360,14 @@ extern "C" int tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_t
     const float* q = pet_tok;
     const int n_inst = 2 * d->depth;
     if (p.fused && d->depth > 0) {
-        const float scale = 1.0f / sqrtf((float)d->dim_head);
-        hipStream_t s = (hipStream_t)stream;
         const size_t pk_stride = up256((size_t)tmf_xf_pack_floats() * 4);
-        float* pf[2 * TMF_FUSION_MAX_DEPTH];
-        for (int i = 0; i < n_inst; ++i) pf[i] = F(base, ip.pk + (size_t)i * pk_stride);
-        TMF_TRY(tmf_xf_launch_pack(n_inst, inst, pf, nullptr, s));
-        {   // K | V of the first instance's context (the pet tokens)
-            tmf_xf_fwd_io io = {};
-            io.x = pet_tok; io.pkv_next = pf[0] + tmf_xf_pack_kv_offset();
-            io.KRn = F(base, ip.KR[0]); io.VCn = F(base, ip.VC[0]);
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, nullptr, &io, scale, 1, d->heads == 8, 1, s));
-        }
-        for (int i = 0; i < n_inst; ++i) {
-            tmf_xf_fwd_io io = {};
-            io.x = (i & 1) ? q : m;
-            io.KR = F(base, ip.KR[i & 1]); io.VC = F(base, ip.VC[i & 1]); io.pk = pf[i];
-            io.mask_o = inst[i].mask_o; io.mask_g = inst[i].mask_g; io.mask_f = inst[i].mask_f;
-            io.y = F(base, ip.tok[i & 1][0]);
-            if (i + 1 < n_inst) {           // this output is the next instance's context
-                io.pkv_next = pf[i + 1] + tmf_xf_pack_kv_offset();
-                io.KRn = F(base, ip.KR[(i + 1) & 1]); io.VCn = F(base, ip.VC[(i + 1) & 1]);
-            }
-            TMF_TRY(tmf_xf_launch_fwd(d->B, d->N, &inst[i], &io, scale, 0, d->heads == 8, 1, s));
-            if (i & 1) q = io.y; else m = io.y;
-        }
-        return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + ip.arg), d->B, d->N, d->dim, stream);
+        auto at = [&](int i) {                      // y over the instance's own input, KR / VC from a ring of two
+            XfInst b = {};
+            b.out.y = F(base, ip.tok[i & 1][0]);
+            b.KR = F(base, ip.KR[i & 1]); b.VC = F(base, ip.VC[i & 1]); b.pk = F(base, ip.pk + (size_t)i * pk_stride);
+            return b;
+        };
+        return fused_fwd(*d, inst, m, q, at, 1, cls, (int32_t*)(base + ip.arg), stream);
     }
     for (int i = 0; i < n_inst; ++i) {
         // mri <- T(mri | pet) + mri, then pet <- T(pet | NEW mri) + pet; the output buffer of a stream alternates per layer
@@ -396,32 +393,17 @@ static int instance_bwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
     // small-parameter gradients share one [row blocks][stride] partial workspace; column order = g.small's layout
     const int o_b2 = 0, o_b1 = dim, o_bo = dim + mlp, o_ln2 = 2 * dim + mlp, o_ln1 = 4 * dim + mlp;
     // Dropout: e_f = m_f dx2 and e_o = m_o dx1 are the dy of the FF2 / to_out Linears (dgrad, bias sums, weight gradients);
-    // the residual paths carry the unmasked dx2 / dx1.  Without a mask e_f = dx2, e_o = dx1.
-    float *ef = dx2, *eo = dx1;
+    // the residual paths carry the unmasked dx2 / dx1.  Without a mask e_f = dx2, e_o = dx1 and nothing writes them a second time.
+    float* ef = w.mask_f ? F(sc, p.s_ef) : dx2;
+    float* eo = w.mask_o ? F(sc, p.s_eo) : dx1;
     // block-final LayerNorm
-    if (w.mask_f) {
-        ef = F(sc, p.s_ef);
-        TMF_TRY(tmf_layernorm_bwd_masked(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, w.mask_f, ef,
-                                         stream));
-    } else {
-        TMF_TRY(tmf_layernorm_bwd(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, stream));
-    }
+    TMF_TRY(tmf_layernorm_bwd_impl(F(sv, I.x2), w.lnf_g, F(sv, I.mf), F(sv, I.rf), dy, dx2, lnpart, R, dim, w.mask_f, ef, stream));
     TMF_TRY(tmf_colsum_finalize(lnpart, p.nblk_ln, 2 * dim, g.lnf, stream));
     // FeedForward
-    if (w.mask_g)
-        TMF_TRY(tmf_tok_linear_bwd_input_masked(ef, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                nullptr, nullptr, part + o_b2, stride, w.mask_g, nullptr, stream));
-    else
-        TMF_TRY(tmf_tok_linear_bwd_input(ef, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, part + o_b2, stride, stream));
-    if (w.mask_o) {
-        eo = F(sc, p.s_eo);
-        TMF_TRY(tmf_tok_linear_bwd_input_masked(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g,
-                                                dx2, nullptr, part + o_ln2, part + o_b1, stride, w.mask_o, eo, stream));
-    } else {
-        TMF_TRY(tmf_tok_linear_bwd_input(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g, dx2,
-                                         nullptr, part + o_ln2, part + o_b1, stride, stream));
-    }
+    TMF_TRY(tmf_tok_linear_bwd_input_impl(ef, w.w2, dh, R, dim, mlp, F(sv, I.h), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, part + o_b2, stride, w.mask_g, nullptr, stream));
+    TMF_TRY(tmf_tok_linear_bwd_input_impl(dh, w.w1, dx1, R, mlp, dim, nullptr, F(sv, I.x1), F(sv, I.m2), F(sv, I.r2), w.ln2_g, dx2,
+                                         nullptr, part + o_ln2, part + o_b1, stride, w.mask_o, eo, stream));
     // Attention
     TMF_TRY(tmf_tok_linear_bwd_input(eo, w.wo, dout, R, dim, inner, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                      nullptr, part + o_bo, stride, stream));
@@ -435,7 +417,8 @@ static int instance_bwd(const tmf_fusion_desc& d, const Plan& p, const tmf_xform
     const float* dys[5] = {ef, dh, eo, dkv, dq};
     const float* xs[5] = {F(sv, I.g), F(sv, I.f), F(sv, I.out), c, F(sv, I.a)};
     float* dws[5] = {g.dw2, g.dw1, g.dwo, g.dwkv, g.dwq};
-    const int Rs[5] = {R, R, R, R, R}, Ns[5] = {dim, mlp, dim, 2 * inner, inner}, Ks[5] = {mlp, dim, inner, dim, dim};
+    int Rs[5] = {R, R, R, R, R}, Ns[5], Ks[5];
+    wgrad_shapes(dim, inner, mlp, Ns, Ks);
     return tmf_tok_wgrad_multi(5, dys, xs, dws, Rs, Ns, Ks, sc + p.s_ws, p.ws_bytes, stream);
 }
 
@@ -528,7 +511,6 @@ extern "C" int tmf_fusion_train_bwd(const tmf_fusion_desc* d, const float* mri_t
         }
         TMF_TRY(tmf_xf_launch_colsum(n_inst, parts, smalls, lnfs, d->B * p.tiles, (hipStream_t)stream));
         // the five weight gradients of every instance: table-driven launches of up to WG_CHUNK problems
-        const int R = p.R, dim = d->dim, inner = p.inner, mlp = d->mlp;
         for (int i0 = 0; i0 < n_inst; i0 += WG_CHUNK / 5) {
             const int ni = (n_inst - i0) < WG_CHUNK / 5 ? (n_inst - i0) : WG_CHUNK / 5;
             const float* dys[WG_CHUNK];
@@ -545,11 +527,8 @@ extern "C" int tmf_fusion_train_bwd(const tmf_fusion_desc* d, const float* mri_t
                 const float* dy5[5] = {F(si, p.s_dx2), F(si, p.s_dh), F(si, p.s_dx1), F(si, p.s_dkv), F(si, p.s_dq)};
                 const float* x5[5] = {F(sv, p.I.g), F(sv, p.I.f), F(sv, p.I.out), ctx, F(sv, p.I.a)};
                 float* dw5[5] = {grads[i].dw2, grads[i].dw1, grads[i].dwo, grads[i].dwkv, grads[i].dwq};
-                const int N5[5] = {dim, mlp, dim, 2 * inner, inner}, K5[5] = {mlp, dim, inner, dim, dim};
-                for (int j = 0; j < 5; ++j) {
-                    dys[5 * k + j] = dy5[j]; xs[5 * k + j] = x5[j]; dws[5 * k + j] = dw5[j];
-                    Rs[5 * k + j] = R; Ns[5 * k + j] = N5[j]; Ks[5 * k + j] = K5[j];
-                }
+                for (int j = 0; j < 5; ++j) { dys[5 * k + j] = dy5[j]; xs[5 * k + j] = x5[j]; dws[5 * k + j] = dw5[j]; Rs[5 * k + j] = p.R; }
+                wgrad_shapes(d->dim, p.inner, d->mlp, Ns + 5 * k, Ks + 5 * k);
             }
             TMF_TRY(tmf_tok_wgrad_multi(5 * ni, dys, xs, dws, Rs, Ns, Ks, sc + p.s_ws, p.ws_bytes, stream));
         }

@@ -110,6 +110,21 @@ long tmf_winox_items(int D, int H, int W, int* swap);     // items per sample (t
 int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3, float* z, float* stat_partial, int B, int D, int H,
                      int W, int cin, int cout, int ncu, hipStream_t stream, const float* scale = nullptr, const float* shift = nullptr,
                      float slope = 0.f, int pool = 0);     // scale != NULL: the eval-mode block (y = LeakyReLU(scale z + shift), pool none | max)
+// token_gemm.hip / token_ops.hip: the one implementation behind each plain / _masked pair of exported entries, for fusion_path.hip
+// to call with whatever mask it has.  mask NULL: the plain entry's launch and name (dx_masked is not looked at), else the _masked one's
+#define TMF_INTERNAL __attribute__((visibility("hidden")))      // not among the library's dynamic symbols
+TMF_INTERNAL
+int tmf_tok_linear_fwd_impl(const float* x, const float* w, const float* bias, const float* residual, float* y, int R, int K,
+                            int Nout, const float* ln_gamma, const float* ln_beta, float eps, float* ln_mean, float* ln_rstd,
+                            float* ln_out, float* gelu_pre, const float* mask, void* stream);
+TMF_INTERNAL
+int tmf_tok_linear_bwd_input_impl(const float* dy, const float* w, float* dx, int R, int Nout, int K, const float* gelu_pre,
+                                 const float* ln_x, const float* ln_mean, const float* ln_rstd, const float* ln_gamma,
+                                 const float* add1, const float* add2, float* ln_partial, float* bias_partial,
+                                 int partial_stride, const float* mask, float* dx_masked, void* stream);
+TMF_INTERNAL
+int tmf_layernorm_bwd_impl(const float* x, const float* gamma, const float* mean, const float* rstd, const float* dy, float* dx,
+                          float* partial, int rows, int dim, const float* mask, float* dx_masked, void* stream);
 
 #define TMF_REQUIRE_PTR(p)                                                     \
     do {                                                                       \
@@ -135,14 +150,20 @@ int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3,
         }                                                                      \
     } while (0)
 
+// TMF_REQUIRE_PTR / TMF_REQUIRE_ALIGNED inside an implementation that several entries share: fn is the calling entry's name
+#define TMF_REQUIRE_PTR_FN(fn, p) TMF_REQUIRE((p) != nullptr, TMF_E_NULL, "%s: argument '%s' is NULL", (fn), #p)
+#define TMF_REQUIRE_ALIGNED_FN(fn, p) \
+    TMF_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15u) == 0, TMF_E_ALIGN, "%s: argument '%s' is not 16-byte aligned", (fn), #p)
+
 // propagate a non-zero status of a library call to the caller
 #define TMF_TRY(call) do { int rc__ = (call); if (rc__ != TMF_OK) return rc__; } while (0)
 
-// Returns 0 or the (positive) hipError_t of the launch that just happened.
-static inline int tmf_launch_result(const char* what) {
+// Returns 0 or the (positive) hipError_t of the launch that just happened.  tag: what a shared implementation adds to the
+// calling entry's name `what`, e.g. "(ln,gelu)".
+static inline int tmf_launch_result(const char* what, const char* tag = "") {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        tmf_set_error("%s: launch failed: %s", what, hipGetErrorString(e));
+        tmf_set_error("%s%s: launch failed: %s", what, tag, hipGetErrorString(e));
         return (int)e;
     }
     return TMF_OK;

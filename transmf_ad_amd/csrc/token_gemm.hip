@@ -298,59 +298,116 @@ __global__ __launch_bounds__(TTHR, 2) void tok_gemm_kernel(const TokArgs p) {   
     }
 }
 
+// fn + tag name the launch in a failure message: the calling entry and its epilogues, "tmf_tok_linear_fwd" "(ln,gelu)"
 template <bool NN, int LNK, int EPI, int CT>
-int launch_tok(const TokArgs& a, hipStream_t s, const char* what) {
+int launch_tok(const TokArgs& a, hipStream_t s, const char* fn, const char* tag) {
     const size_t lds = (size_t)(TM * (a.K + 4) + 4 * 16 * 2) * 4;
     hipLaunchKernelGGL((tok_gemm_kernel<NN, LNK, EPI, CT>), dim3(tmf_cdiv(a.R, TM), a.N / (64 * CT)), dim3(TTHR), lds, s, a);
-    return tmf_launch_result(what);
+    return tmf_launch_result(fn, tag);
 }
 
-// forward: 128-column tiles wherever Nout allows them (every shape accepted before 64-wide outputs were), else 64
-template <int LNK, int EPI>
-int launch_fwd(const TokArgs& a, hipStream_t s, const char* what) {
-    return a.N % 128 == 0 ? launch_tok<false, LNK, EPI, 2>(a, s, what) : launch_tok<false, LNK, EPI, 1>(a, s, what);
+// element-wise epilogues, either direction: 128-column tiles wherever the output width allows them, else 64
+template <bool NN, int LNK, int EPI>
+int launch_wide(const TokArgs& a, hipStream_t s, const char* fn, const char* tag) {
+    return a.N % 128 == 0 ? launch_tok<NN, LNK, EPI, 2>(a, s, fn, tag) : launch_tok<NN, LNK, EPI, 1>(a, s, fn, tag);
+}
+
+// ... and with a keep-mask the *_MASK instance of the same epilogue: EPI_x_MASK == EPI_x + EPI_PLAIN_MASK
+static_assert(EPI_GELU_MASK == EPI_GELU + EPI_PLAIN_MASK && EPI_GELU_GRAD_MASK == EPI_GELU_GRAD + EPI_PLAIN_MASK, "order");
+template <bool NN, int LNK, int EPI>
+int launch_wide_opt_mask(const TokArgs& a, hipStream_t s, const char* fn, const char* tag) {
+    return a.mask != nullptr ? launch_wide<NN, LNK, EPI + EPI_PLAIN_MASK>(a, s, fn, tag) : launch_wide<NN, LNK, EPI>(a, s, fn, tag);
 }
 
 template <int LNK>
-int launch_fwd_ln(const TokArgs& a, bool gelu, hipStream_t s) {
-    if (gelu) return launch_fwd<LNK, EPI_GELU>(a, s, "tmf_tok_linear_fwd(ln,gelu)");
-    return launch_fwd<LNK, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd(ln)");
+int launch_fwd(const TokArgs& a, hipStream_t s, const char* fn) {
+    if (a.pre != nullptr) return launch_wide_opt_mask<false, LNK, EPI_GELU>(a, s, fn, LNK != 0 ? "(ln,gelu)" : "(gelu)");
+    return launch_wide_opt_mask<false, LNK, EPI_PLAIN>(a, s, fn, LNK != 0 ? "(ln)" : "");
 }
 
-// backward input gradient, element-wise epilogues: the forward's rule over the output width K
-template <int EPI>
-int launch_bwd(const TokArgs& a, hipStream_t s, const char* what) {
-    return a.N % 128 == 0 ? launch_tok<true, 0, EPI, 2>(a, s, what) : launch_tok<true, 0, EPI, 1>(a, s, what);
+// LayerNorm-backward epilogue: one workgroup per row block holds whole rows, the tile is K = 64 CT wide
+template <int CT>
+int launch_ln_bwd(const TokArgs& a, hipStream_t s, const char* fn) {
+    if (a.mask != nullptr) return launch_tok<true, 0, EPI_LN_BWD_MASK, CT>(a, s, fn, "(ln)");
+    return launch_tok<true, 0, EPI_LN_BWD, CT>(a, s, fn, "(ln)");
 }
 
 }  // namespace
 
 extern "C" int tmf_tok_row_blocks(int R) { return R > 0 ? tmf_cdiv(R, TM) : 0; }
 
+// tmf_tok_linear_fwd (mask NULL) and tmf_tok_linear_fwd_masked (tmf_common.h)
+int tmf_tok_linear_fwd_impl(const float* x, const float* w, const float* bias, const float* residual, float* y, int R, int K,
+                            int Nout, const float* ln_gamma, const float* ln_beta, float eps, float* ln_mean, float* ln_rstd,
+                            float* ln_out, float* gelu_pre, const float* mask, void* stream) {
+    const char* fn = mask != nullptr ? "tmf_tok_linear_fwd_masked" : "tmf_tok_linear_fwd";
+    TMF_REQUIRE_PTR_FN(fn, x); TMF_REQUIRE_PTR_FN(fn, w); TMF_REQUIRE_PTR_FN(fn, y);
+    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "%s: non-positive dimension", fn);
+    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % 64 == 0, TMF_E_SHAPE,
+                "%s: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 64", fn, K, Nout);
+    TMF_REQUIRE(gelu_pre == nullptr || residual == nullptr, TMF_E_SHAPE, "%s: GELU epilogue takes no residual", fn);
+    TokArgs a = {};
+    a.A = x; a.W = w; a.Y = y; a.R = R; a.K = K; a.N = Nout;
+    a.bias = bias; a.res = residual; a.pre = gelu_pre; a.mask = mask;
+    hipStream_t s = (hipStream_t)stream;
+    if (ln_gamma == nullptr) return launch_fwd<0>(a, s, fn);
+    TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE, "%s: the LayerNorm prologue needs K of 64, 128 or 256 (got %d)", fn, K);
+    TMF_REQUIRE_PTR_FN(fn, ln_beta); TMF_REQUIRE_PTR_FN(fn, ln_mean); TMF_REQUIRE_PTR_FN(fn, ln_rstd);
+    a.ln_g = ln_gamma; a.ln_b = ln_beta; a.eps = eps; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_out = ln_out;
+    if (K == 64) return launch_fwd<64>(a, s, fn);
+    if (K == 128) return launch_fwd<128>(a, s, fn);
+    return launch_fwd<256>(a, s, fn);
+}
+
+// tmf_tok_linear_bwd_input (mask NULL; dx_masked is then not looked at) and tmf_tok_linear_bwd_input_masked (tmf_common.h)
+int tmf_tok_linear_bwd_input_impl(const float* dy, const float* w, float* dx, int R, int Nout, int K, const float* gelu_pre,
+                                  const float* ln_x, const float* ln_mean, const float* ln_rstd, const float* ln_gamma,
+                                  const float* add1, const float* add2, float* ln_partial, float* bias_partial,
+                                  int partial_stride, const float* mask, float* dx_masked, void* stream) {
+    const char* fn = mask != nullptr ? "tmf_tok_linear_bwd_input_masked" : "tmf_tok_linear_bwd_input";
+    TMF_REQUIRE_PTR_FN(fn, dy); TMF_REQUIRE_PTR_FN(fn, w); TMF_REQUIRE_PTR_FN(fn, dx);
+    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "%s: non-positive dimension", fn);
+    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % 64 == 0, TMF_E_SHAPE,
+                "%s: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 64", fn, Nout, K);
+    TMF_REQUIRE((ln_partial == nullptr && bias_partial == nullptr) || partial_stride > 0, TMF_E_SHAPE,
+                "%s: partial_stride must be positive", fn);
+    const bool masked = mask != nullptr, gelu = gelu_pre != nullptr;
+    // neither epilogue is the plain input gradient, which has no *_MASK instance (the block's Dropouts sit elsewhere)
+    TMF_REQUIRE(!masked || gelu != (ln_x != nullptr), TMF_E_SHAPE,
+                "%s: needs exactly one of the GELU-gradient and LayerNorm-backward epilogues", fn);
+    TokArgs a = {};
+    a.A = dy; a.W = w; a.Y = dx; a.R = R; a.K = Nout; a.N = K;       // contraction over dy's columns
+    a.gelu_h = gelu_pre; a.add1 = add1; a.add2 = add2;
+    a.lnb_partial = ln_partial; a.colsum_partial = bias_partial; a.partial_stride = partial_stride;
+    if (masked) { a.mask = mask; a.Y2 = dx_masked; }
+    hipStream_t s = (hipStream_t)stream;
+    if (ln_x != nullptr) {
+        // both epilogues together are refused here without a mask; with one the rule above already has, so only K is named
+        TMF_REQUIRE((K == 64 || K == 128 || K == 256) && !gelu, TMF_E_SHAPE,
+                    "%s: the LayerNorm-backward epilogue needs K of 64, 128 or 256%s (K=%d)", fn, masked ? "" : " and no GELU", K);
+        TMF_REQUIRE_PTR_FN(fn, ln_mean); TMF_REQUIRE_PTR_FN(fn, ln_rstd); TMF_REQUIRE_PTR_FN(fn, ln_gamma);
+        if (masked) TMF_REQUIRE_PTR_FN(fn, dx_masked);               // the masked copy is all the mask is for here
+        a.lnb_x = ln_x; a.lnb_mean = ln_mean; a.lnb_rstd = ln_rstd; a.lnb_g = ln_gamma;
+        if (K == 64) return launch_ln_bwd<1>(a, s, fn);
+        if (K == 128) return launch_ln_bwd<2>(a, s, fn);
+        return launch_ln_bwd<4>(a, s, fn);
+    }
+    if (gelu) {
+        // this epilogue reads none of the three: the plain entry has always let add1 / add2 pass unused, the masked one refuses them
+        TMF_REQUIRE(!masked || (add1 == nullptr && add2 == nullptr && dx_masked == nullptr), TMF_E_SHAPE,
+                    "%s: the GELU-gradient epilogue takes no add1, add2 or dx_masked", fn);
+        return launch_wide_opt_mask<true, 0, EPI_GELU_GRAD>(a, s, fn, "(gelu)");
+    }
+    a.res = add1;                                                    // plain epilogue: + add1 (one residual gradient)
+    TMF_REQUIRE(add2 == nullptr, TMF_E_SHAPE, "%s: add2 needs the LayerNorm epilogue", fn);
+    return launch_wide<true, 0, EPI_PLAIN>(a, s, fn, "");
+}
+
 extern "C" int tmf_tok_linear_fwd(const float* x, const float* w, const float* bias, const float* residual, float* y,
                                   int R, int K, int Nout, const float* ln_gamma, const float* ln_beta, float eps,
                                   float* ln_mean, float* ln_rstd, float* ln_out, float* gelu_pre, void* stream) {
-    TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(y);
-    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_fwd: non-positive dimension");
-    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % 64 == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_fwd: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 64", K, Nout);
-    TokArgs a = {};
-    a.A = x; a.W = w; a.Y = y; a.R = R; a.K = K; a.N = Nout;
-    a.bias = bias; a.res = residual; a.pre = gelu_pre;
-    hipStream_t s = (hipStream_t)stream;
-    if (gelu_pre != nullptr)
-        TMF_REQUIRE(residual == nullptr, TMF_E_SHAPE, "tmf_tok_linear_fwd: GELU epilogue takes no residual");
-    if (ln_gamma != nullptr) {
-        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
-                    "tmf_tok_linear_fwd: the LayerNorm prologue needs K of 64, 128 or 256 (got %d)", K);
-        TMF_REQUIRE_PTR(ln_beta); TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd);
-        a.ln_g = ln_gamma; a.ln_b = ln_beta; a.eps = eps; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_out = ln_out;
-        if (K == 64) return launch_fwd_ln<64>(a, gelu_pre != nullptr, s);
-        if (K == 128) return launch_fwd_ln<128>(a, gelu_pre != nullptr, s);
-        return launch_fwd_ln<256>(a, gelu_pre != nullptr, s);
-    }
-    if (gelu_pre != nullptr) return launch_fwd<0, EPI_GELU>(a, s, "tmf_tok_linear_fwd(gelu)");
-    return launch_fwd<0, EPI_PLAIN>(a, s, "tmf_tok_linear_fwd");
+    return tmf_tok_linear_fwd_impl(x, w, bias, residual, y, R, K, Nout, ln_gamma, ln_beta, eps, ln_mean, ln_rstd, ln_out, gelu_pre,
+                                   nullptr, stream);
 }
 
 extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* dx, int R, int Nout, int K,
@@ -358,61 +415,18 @@ extern "C" int tmf_tok_linear_bwd_input(const float* dy, const float* w, float* 
                                         const float* ln_rstd, const float* ln_gamma, const float* add1,
                                         const float* add2, float* ln_partial, float* bias_partial,
                                         int partial_stride, void* stream) {
-    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(dx);
-    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_bwd_input: non-positive dimension");
-    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % 64 == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 64", Nout, K);
-    TMF_REQUIRE((ln_partial == nullptr && bias_partial == nullptr) || partial_stride > 0, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input: partial_stride must be positive");
-    TokArgs a = {};
-    a.A = dy; a.W = w; a.Y = dx; a.R = R; a.K = Nout; a.N = K;       // contraction over dy's columns
-    a.gelu_h = gelu_pre; a.add1 = add1; a.add2 = add2;
-    a.lnb_partial = ln_partial; a.colsum_partial = bias_partial; a.partial_stride = partial_stride;
-    hipStream_t s = (hipStream_t)stream;
-    if (ln_x != nullptr) {
-        TMF_REQUIRE((K == 64 || K == 128 || K == 256) && gelu_pre == nullptr, TMF_E_SHAPE,
-                    "tmf_tok_linear_bwd_input: the LayerNorm-backward epilogue needs K of 64, 128 or 256 and no GELU (K=%d)", K);
-        TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd); TMF_REQUIRE_PTR(ln_gamma);
-        a.lnb_x = ln_x; a.lnb_mean = ln_mean; a.lnb_rstd = ln_rstd; a.lnb_g = ln_gamma;
-        // one workgroup per row block holds whole rows: the tile is K wide
-        if (K == 64) return launch_tok<true, 0, EPI_LN_BWD, 1>(a, s, "tmf_tok_linear_bwd_input(ln)");
-        if (K == 128) return launch_tok<true, 0, EPI_LN_BWD, 2>(a, s, "tmf_tok_linear_bwd_input(ln)");
-        return launch_tok<true, 0, EPI_LN_BWD, 4>(a, s, "tmf_tok_linear_bwd_input(ln)");
-    }
-    if (gelu_pre != nullptr) return launch_bwd<EPI_GELU_GRAD>(a, s, "tmf_tok_linear_bwd_input(gelu)");
-    a.res = add1;                                                    // plain epilogue: + add1 (one residual gradient)
-    TMF_REQUIRE(add2 == nullptr, TMF_E_SHAPE, "tmf_tok_linear_bwd_input: add2 needs the LayerNorm epilogue");
-    return launch_bwd<EPI_PLAIN>(a, s, "tmf_tok_linear_bwd_input");
+    return tmf_tok_linear_bwd_input_impl(dy, w, dx, R, Nout, K, gelu_pre, ln_x, ln_mean, ln_rstd, ln_gamma, add1, add2, ln_partial,
+                                         bias_partial, partial_stride, nullptr, nullptr, stream);
 }
 
-// The Dropout forms of the two entries above: the same tiles and checks, the *_MASK epilogue instances.
+// The Dropout forms require the mask that selects them.  A NULL one is reported where it always was, after the pointers ahead of it.
 extern "C" int tmf_tok_linear_fwd_masked(const float* x, const float* w, const float* bias, const float* residual, float* y,
                                          int R, int K, int Nout, const float* ln_gamma, const float* ln_beta, float eps,
                                          float* ln_mean, float* ln_rstd, float* ln_out, float* gelu_pre, const float* mask,
                                          void* stream) {
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(y); TMF_REQUIRE_PTR(mask);
-    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_fwd_masked: non-positive dimension");
-    TMF_REQUIRE(K % 16 == 0 && K <= 2048 && Nout % 64 == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_fwd_masked: K=%d must be a multiple of 16 (<= 2048) and Nout=%d a multiple of 64", K, Nout);
-    TMF_REQUIRE(gelu_pre == nullptr || residual == nullptr, TMF_E_SHAPE,
-                "tmf_tok_linear_fwd_masked: GELU epilogue takes no residual");
-    TokArgs a = {};
-    a.A = x; a.W = w; a.Y = y; a.R = R; a.K = K; a.N = Nout;
-    a.bias = bias; a.res = residual; a.pre = gelu_pre; a.mask = mask;
-    hipStream_t s = (hipStream_t)stream;
-    const bool gelu = gelu_pre != nullptr;
-    if (ln_gamma != nullptr) {
-        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
-                    "tmf_tok_linear_fwd_masked: the LayerNorm prologue needs K of 64, 128 or 256 (got %d)", K);
-        TMF_REQUIRE_PTR(ln_beta); TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd);
-        a.ln_g = ln_gamma; a.ln_b = ln_beta; a.eps = eps; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_out = ln_out;
-        const char* what = gelu ? "tmf_tok_linear_fwd_masked(ln,gelu)" : "tmf_tok_linear_fwd_masked(ln)";
-        if (K == 64) return gelu ? launch_fwd<64, EPI_GELU_MASK>(a, s, what) : launch_fwd<64, EPI_PLAIN_MASK>(a, s, what);
-        if (K == 128) return gelu ? launch_fwd<128, EPI_GELU_MASK>(a, s, what) : launch_fwd<128, EPI_PLAIN_MASK>(a, s, what);
-        return gelu ? launch_fwd<256, EPI_GELU_MASK>(a, s, what) : launch_fwd<256, EPI_PLAIN_MASK>(a, s, what);
-    }
-    if (gelu) return launch_fwd<0, EPI_GELU_MASK>(a, s, "tmf_tok_linear_fwd_masked(gelu)");
-    return launch_fwd<0, EPI_PLAIN_MASK>(a, s, "tmf_tok_linear_fwd_masked");
+    return tmf_tok_linear_fwd_impl(x, w, bias, residual, y, R, K, Nout, ln_gamma, ln_beta, eps, ln_mean, ln_rstd, ln_out, gelu_pre,
+                                   mask, stream);
 }
 
 extern "C" int tmf_tok_linear_bwd_input_masked(const float* dy, const float* w, float* dx, int R, int Nout, int K,
@@ -421,30 +435,8 @@ extern "C" int tmf_tok_linear_bwd_input_masked(const float* dy, const float* w, 
                                                const float* add2, float* ln_partial, float* bias_partial,
                                                int partial_stride, const float* mask, float* dx_masked, void* stream) {
     TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(mask);
-    TMF_REQUIRE(R > 0 && K > 0 && Nout > 0, TMF_E_SHAPE, "tmf_tok_linear_bwd_input_masked: non-positive dimension");
-    TMF_REQUIRE(Nout % 16 == 0 && Nout <= 2048 && K % 64 == 0, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input_masked: Nout=%d must be a multiple of 16 (<= 2048) and K=%d a multiple of 64", Nout, K);
-    TMF_REQUIRE((ln_partial == nullptr && bias_partial == nullptr) || partial_stride > 0, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input_masked: partial_stride must be positive");
-    TMF_REQUIRE((gelu_pre != nullptr) != (ln_x != nullptr), TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input_masked: needs exactly one of the GELU-gradient and LayerNorm-backward epilogues");
-    TokArgs a = {};
-    a.A = dy; a.W = w; a.Y = dx; a.R = R; a.K = Nout; a.N = K;       // contraction over dy's columns
-    a.gelu_h = gelu_pre; a.add1 = add1; a.add2 = add2; a.mask = mask; a.Y2 = dx_masked;
-    a.lnb_partial = ln_partial; a.colsum_partial = bias_partial; a.partial_stride = partial_stride;
-    hipStream_t s = (hipStream_t)stream;
-    if (ln_x != nullptr) {
-        TMF_REQUIRE(K == 64 || K == 128 || K == 256, TMF_E_SHAPE,
-                    "tmf_tok_linear_bwd_input_masked: the LayerNorm-backward epilogue needs K of 64, 128 or 256 (K=%d)", K);
-        TMF_REQUIRE_PTR(ln_mean); TMF_REQUIRE_PTR(ln_rstd); TMF_REQUIRE_PTR(ln_gamma); TMF_REQUIRE_PTR(dx_masked);
-        a.lnb_x = ln_x; a.lnb_mean = ln_mean; a.lnb_rstd = ln_rstd; a.lnb_g = ln_gamma;
-        if (K == 64) return launch_tok<true, 0, EPI_LN_BWD_MASK, 1>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
-        if (K == 128) return launch_tok<true, 0, EPI_LN_BWD_MASK, 2>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
-        return launch_tok<true, 0, EPI_LN_BWD_MASK, 4>(a, s, "tmf_tok_linear_bwd_input_masked(ln)");
-    }
-    TMF_REQUIRE(add1 == nullptr && add2 == nullptr && dx_masked == nullptr, TMF_E_SHAPE,
-                "tmf_tok_linear_bwd_input_masked: the GELU-gradient epilogue takes no add1, add2 or dx_masked");
-    return launch_bwd<EPI_GELU_GRAD_MASK>(a, s, "tmf_tok_linear_bwd_input_masked(gelu)");
+    return tmf_tok_linear_bwd_input_impl(dy, w, dx, R, Nout, K, gelu_pre, ln_x, ln_mean, ln_rstd, ln_gamma, add1, add2, ln_partial,
+                                         bias_partial, partial_stride, mask, dx_masked, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------

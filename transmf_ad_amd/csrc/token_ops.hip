@@ -364,35 +364,40 @@ extern "C" int tmf_layernorm_bwd_blocks(int rows, int dim) {
     return tmf_cdiv(rows, ln_rows_per_block(rows));
 }
 
-extern "C" int tmf_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd,
-                                 const float* dy, float* dx, float* partial, int rows, int dim, void* stream) {
-    TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(gamma); TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(rstd);
-    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(partial);
-    TMF_REQUIRE(rows > 0 && dim > 0, TMF_E_SHAPE, "tmf_layernorm_bwd: rows=%d dim=%d", rows, dim);
+// tmf_layernorm_bwd (mask NULL; dx_masked is then not looked at) and tmf_layernorm_bwd_masked (tmf_common.h)
+int tmf_layernorm_bwd_impl(const float* x, const float* gamma, const float* mean, const float* rstd, const float* dy, float* dx,
+                           float* partial, int rows, int dim, const float* mask, float* dx_masked, void* stream) {
+    const char* fn = mask != nullptr ? "tmf_layernorm_bwd_masked" : "tmf_layernorm_bwd";
+    TMF_REQUIRE_PTR_FN(fn, x); TMF_REQUIRE_PTR_FN(fn, gamma); TMF_REQUIRE_PTR_FN(fn, mean); TMF_REQUIRE_PTR_FN(fn, rstd);
+    TMF_REQUIRE_PTR_FN(fn, dy); TMF_REQUIRE_PTR_FN(fn, dx); TMF_REQUIRE_PTR_FN(fn, partial);
+    if (mask != nullptr) TMF_REQUIRE_PTR_FN(fn, dx_masked);
+    TMF_REQUIRE(rows > 0 && dim > 0, TMF_E_SHAPE, "%s: rows=%d dim=%d", fn, rows, dim);
     const int vec = dim % 4 == 0 ? 4 : 1;
-    TMF_REQUIRE(dim <= 64 * vec * LN_MAXV, TMF_E_SHAPE, "tmf_layernorm_bwd: dim=%d exceeds %d", dim, 64 * vec * LN_MAXV);
+    TMF_REQUIRE(dim <= 64 * vec * LN_MAXV, TMF_E_SHAPE, "%s: dim=%d exceeds %d", fn, dim, 64 * vec * LN_MAXV);
     const int rpb = ln_rows_per_block(rows);
     dim3 grid(tmf_cdiv(rows, rpb)), block(256);
     const size_t lds = (size_t)8 * dim * 4;
-    if (vec == 4) hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb);
-    else          hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb);
-    return tmf_launch_result("tmf_layernorm_bwd");
+    if (mask == nullptr) dx_masked = nullptr;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb, mask, dx_masked);
+    };
+    if (mask != nullptr) vec == 4 ? launch(layernorm_bwd_kernel<4, true>) : launch(layernorm_bwd_kernel<1, true>);
+    else                 vec == 4 ? launch(layernorm_bwd_kernel<4, false>) : launch(layernorm_bwd_kernel<1, false>);
+    return tmf_launch_result(fn);
 }
 
+extern "C" int tmf_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd,
+                                 const float* dy, float* dx, float* partial, int rows, int dim, void* stream) {
+    return tmf_layernorm_bwd_impl(x, gamma, mean, rstd, dy, dx, partial, rows, dim, nullptr, nullptr, stream);
+}
+
+// The Dropout form: mask and the masked copy are required, and reported where they always were, after the pointers ahead of them.
 extern "C" int tmf_layernorm_bwd_masked(const float* x, const float* gamma, const float* mean, const float* rstd,
                                         const float* dy, float* dx, float* partial, int rows, int dim,
                                         const float* mask, float* dx_masked, void* stream) {
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(gamma); TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(rstd);
-    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(partial); TMF_REQUIRE_PTR(mask); TMF_REQUIRE_PTR(dx_masked);
-    TMF_REQUIRE(rows > 0 && dim > 0, TMF_E_SHAPE, "tmf_layernorm_bwd_masked: rows=%d dim=%d", rows, dim);
-    const int vec = dim % 4 == 0 ? 4 : 1;
-    TMF_REQUIRE(dim <= 64 * vec * LN_MAXV, TMF_E_SHAPE, "tmf_layernorm_bwd_masked: dim=%d exceeds %d", dim, 64 * vec * LN_MAXV);
-    const int rpb = ln_rows_per_block(rows);
-    dim3 grid(tmf_cdiv(rows, rpb)), block(256);
-    const size_t lds = (size_t)8 * dim * 4;
-    if (vec == 4) hipLaunchKernelGGL((layernorm_bwd_kernel<4, true>), grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb, mask, dx_masked);
-    else          hipLaunchKernelGGL((layernorm_bwd_kernel<1, true>), grid, block, lds, (hipStream_t)stream, x, gamma, mean, rstd, dy, dx, partial, rows, dim, rpb, mask, dx_masked);
-    return tmf_launch_result("tmf_layernorm_bwd_masked");
+    TMF_REQUIRE_PTR(dy); TMF_REQUIRE_PTR(dx); TMF_REQUIRE_PTR(partial); TMF_REQUIRE_PTR(mask);
+    return tmf_layernorm_bwd_impl(x, gamma, mean, rstd, dy, dx, partial, rows, dim, mask, dx_masked, stream);
 }
 
 extern "C" int tmf_mask_mul(const float* x, const float* mask, float* y, long n, void* stream) {
