@@ -52,8 +52,10 @@ class Arena:
     def ptr(self, name):
         return self.base + self.slots[name][0]
 
-    def fetch(self):
-        """Synchronise, check the bytes outside the outputs, return {output name: host tensor}."""
+    def fetch(self, may_nan=(), workspace=()):
+        """Synchronise, check the bytes outside the outputs, return {output name: host tensor}.  `may_nan`: outputs whose
+        values may be NaN by computation (they must still be fully written: no element keeps the fill pattern, which no
+        arithmetic produces); `workspace`: scratch slots - their surroundings are checked, their content is not judged."""
         torch.cuda.synchronize()
         back = self.dev.cpu()
         at = 0
@@ -66,7 +68,13 @@ class Arena:
         for name in self.out_names:
             off, n, dtype, shape = self.slots[name]
             res[name] = back[off:off + n].view(dtype).view(shape)
-            assert not torch.isnan(res[name]).any(), f"'{name}' holds NaN (unwritten or computed)"
+            if name in workspace:
+                continue
+            if name in may_nan or not dtype.is_floating_point:
+                word = {2: torch.int16, 4: torch.int32}[torch.empty(0, dtype=dtype).element_size()]
+                assert not bool((back[off:off + n].view(word) == -1).any()), f"'{name}' holds unwritten elements"
+            else:
+                assert not torch.isnan(res[name]).any(), f"'{name}' holds NaN (unwritten or computed)"
         return res
 
 

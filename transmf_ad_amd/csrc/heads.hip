@@ -324,9 +324,9 @@ __global__ __launch_bounds__(HT) void heads_fwd_kernel(HeadsArgs a) {
                 }
         }
     }
-        // ---- fc_cls.8 (its small weight matrix staged in LDS: l_a1 is free by now) ----
+        // ---- fc_cls.8 (its small weight matrix staged in LDS behind l_a2: NC * H2 may exceed the B * H1 floats of l_a1) ----
         __syncthreads();
-        float* l_w8 = l_a1;                         // [NC][H2]
+        float* l_w8 = l_a2 + B * a.H2;              // [NC][H2]
         for (int e = t; e < a.NC * a.H2; e += HT) l_w8[e] = a.w8[e];
         __syncthreads();
         for (int e = t; e < B * a.NC; e += HT) {
@@ -891,12 +891,9 @@ int check_heads(const char* fn, const tmf_heads_desc* d) {
     return TMF_OK;
 }
 size_t fwd_lds(const tmf_heads_desc& d) {
-    const size_t fc = (size_t)d.B * d.H1 + (size_t)d.B * d.H2;
-    const size_t fc8 = (size_t)d.NC * d.H2;                                     // fc_cls.8's weights re-use l_a1
+    const size_t fc = (size_t)d.B * d.H1 + (size_t)d.B * d.H2 + (size_t)d.NC * d.H2;   // l_a1, l_a2, fc_cls.8's weights
     const size_t dd = (size_t)d.NC * d.HD + 2 * d.B * d.dim + 2 * d.B * d.HD + 4 * d.HD;
-    size_t n = fc > dd ? fc : dd;
-    if (n < fc8) n = fc8;
-    return n * 4;
+    return (fc > dd ? fc : dd) * 4;
 }
 size_t bwd_lds(const tmf_heads_desc& d) {
     const size_t fc = (size_t)d.B * d.H2 + (size_t)8 * d.B * 64;               // dz2 + the j-slice partials of the fc_cls.4 backward
