@@ -223,6 +223,7 @@ int    tmf_conv3d_c1_wgrad(const float* x, const float* dz, float* dw, void* wor
  *   tmf_c1_bn_pool_fwd  -> pooled
  *   tmf_c1_bwd_reduce   -> partial [tmf_c1_blocks()][2][C]       (reduce with tmf_bn_bwd_finalize)
  *   tmf_c1_bwd_wgrad    -> dw[27][C]   (coef from tmf_bn_bwd_finalize)
+ *   tmf_c1_bwd_dgrad    -> dx[b][d][h][w] (coef from tmf_bn_bwd_finalize; all-zero coef = eval-mode BatchNorm; fp32 tensors)
  * ---------------------------------------------------------------------------- */
 int    tmf_c1_blocks(int B, int D, int H, int W, int C);
 int    tmf_c1_stats(const float* x, const float* w, float* stat_partial, int B, int D, int H, int W, int C, void* stream);
@@ -267,6 +268,11 @@ int    tmf_c1_bwd_fused_route(const float* x, const float* w, const float* scale
                               const float* invstd, const float* dpool, const float* z_sel, const unsigned char* arg,
                               const void* gram, float* dw, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                               int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream);
+/* tmf_c1_bwd_fused[_route] that also writes coef [2][C] for tmf_c1_bwd_dgrad (z_sel = arg = NULL: the recomputing form) */
+int    tmf_c1_bwd_fused_coef(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, const float* dpool, const float* z_sel, const unsigned char* arg,
+                             const void* gram, float* dw, float* dgamma, float* dbeta, float* coef, void* workspace,
+                             size_t workspace_bytes, int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream);
 int    tmf_c1_bwd_reduce(const float* x, const float* w, const float* scale, const float* shift,
                          const float* mean, const float* invstd, const float* dpool, float* partial,
                          int B, int D, int H, int W, int C, float slope, void* stream);
@@ -275,6 +281,15 @@ int    tmf_c1_bwd_wgrad(const float* x, const float* w, const float* scale, cons
                         const float* mean, const float* invstd, const float* coef, const float* dpool,
                         float* dw, void* workspace, size_t workspace_bytes,
                         int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream);
+/* Data gradient of the block (csrc/conv1_dgrad.hip): with dy the routed, LeakyReLU-masked dpool (first maximum of y, the
+ * forward's routing bit for bit under the same "c1_split" setting) and dz_c = scale_c (dy_c - coef[0][c] - coef[1][c] invstd_c
+ * (z_c - mean_c)) on EVERY voxel, dx(u) = sum_t sum_c w[t][c] dz_c(u - t + 1).  Nothing of size voxels x C touches memory; the
+ * result is bit-reproducible.  Any D, H, W, C >= 1; an empty pooled tensor (dpool may then be NULL) leaves the BatchNorm part.
+ * workspace: tmf_c1_bwd_dgrad_workspace_bytes() (a few KB of prepared stencil coefficients). */
+size_t tmf_c1_bwd_dgrad_workspace_bytes(int B, int D, int H, int W, int C);
+int    tmf_c1_bwd_dgrad(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                        const float* invstd, const float* coef, const float* dpool, float* dx,
+                        void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int C, float slope, void* stream);
 /* The same four passes with both products on the bf16 matrix cores (operands rounded to bf16, fp32 accumulation):
  * 2 MFMAs per tile instead of 14 / 16.  Same arguments, same workspace / block counts; pooled_bf16 != 0: the pooled
  * output / its gradient dpool are bf16 tensors (bf16 activation storage, BASELINE configs[2]). */
@@ -565,7 +580,10 @@ int    tmf_batch_augment(const float* store_mri, const float* store_pet, const i
  *   tmf_snet_train_bwd : dout (same shape as out) -> gradients written into g: dweight[l] in the nn.Conv3d layout,
  *                        dbias[l] (exact zeros: a bias ahead of batch-statistics BatchNorm), dgamma[l], dbeta[l].  NULL
  *                        dweight / dbias entries are skipped.  `scratch` >= tmf_snet_bwd_scratch_bytes, free afterwards.
- * There is no gradient for vol (the network input needs none: kfold_train_adversarial.py:106-107).
+ *   tmf_snet_train_bwd_input : tmf_snet_train_bwd plus dvol [B][D][H][W], the gradient for vol (saliency, input-gradient
+ *                        regularisers; training itself needs none: kfold_train_adversarial.py:106-107).  Block 0 then also runs
+ *                        tmf_c1_bwd_dgrad on block 1's data gradient; fp32 and fp32x precisions (bf16: TMF_E_ARG).  dvol = NULL is
+ *                        tmf_snet_train_bwd, launch for launch.  Same scratch (tmf_snet_bwd_scratch_bytes covers both).
  * ---------------------------------------------------------------------------- */
 #define TMF_SNET_BLOCKS 7
 #define TMF_PREC_FP32 0
@@ -633,6 +651,9 @@ int    tmf_snet_train_fwd(const tmf_snet_desc* d, const float* vol, const tmf_sn
                           void* saved, size_t saved_bytes, float* out, void* stream);
 int    tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, const void* saved, size_t saved_bytes,
                           const float* dout, const tmf_snet_grads* grads, void* scratch, size_t scratch_bytes, void* stream);
+int    tmf_snet_train_bwd_input(const tmf_snet_desc* d, const float* vol, const void* saved, size_t saved_bytes,
+                                const float* dout, const tmf_snet_grads* grads, void* scratch, size_t scratch_bytes, void* stream,
+                                float* dvol);
 /* Inference form (val_step, kfold_train_adversarial.py:144-161; eval-mode BatchNorm folded into each block's single
  * conv + BN + LeakyReLU + pool kernel): one call per encoder, fp32 precision, running statistics required; `workspace`
  * (>= tmf_snet_eval_workspace_bytes) is scratch. */

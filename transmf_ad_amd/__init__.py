@@ -17,6 +17,7 @@ from .pipeline import DeviceDataset, DevicePrefetcher, scale_intensity_flip, rot
 from .nifti import read_nifti, write_nifti, nifti_batches         # noqa: F401
 from . import optim                                                  # noqa: F401
 from .losses import FALoss, SupConLoss                               # noqa: F401
+from .saliency import input_gradients, integrated_gradients        # noqa: F401
 from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, FeedForward, PreNorm,   # noqa: F401
                        Transformer, sNet)
 
@@ -24,4 +25,5 @@ __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_trans
            "CrossTransformer", "CrossTransformer_MOD_AVG", "Transformer",
            "Attention", "PreNorm", "FeedForward", "revgrad", "GradientReversal", "load_library", "TmfError",
            "set_conv_precision", "get_conv_precision", "set_activation_storage", "DeviceDataset", "DevicePrefetcher", "scale_intensity_flip", "rotate_zoom",
-           "read_nifti", "write_nifti", "nifti_batches", "FALoss", "SupConLoss"]
+           "read_nifti", "write_nifti", "nifti_batches", "FALoss", "SupConLoss",
+           "input_gradients", "integrated_gradients"]

@@ -18,24 +18,15 @@
 // directly the MFMA B operand (k = lane half) — no LDS round trip, no shuffles.
 //
 // Replaces, for networks.py:21-26 (sNet.conv1): aten::conv3d, batch_norm, leaky_relu, max_pool3d and their
-// backward (weight gradient only: the network input needs no gradient, kfold_train_adversarial.py:106).
+// backward (here: the weight gradient — training needs no more, kfold_train_adversarial.py:106; the data gradient for saliency
+// and input-gradient regularisers is conv1_dgrad.hip, which shares this file's z through conv1_z.h).
 #include <type_traits>
-#include "tmf_device.h"
+#include "conv1_z.h"       // brick geometry, LDS images, operand fragments and the MFMA sequences of z: shared with conv1_dgrad.hip
 
 namespace {
-
-#ifndef TMF_C1_TD
-#define TMF_C1_TD 4
-#endif
-constexpr int TD = TMF_C1_TD, TH = 8, TW = 8;
-constexpr int NTI = TD / 2;                           // M-tiles per wave and brick (4 waves, TD * 2 tiles of 32 voxels)
-constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;
-constexpr int NHALO = HD * HH * HW;
+using namespace c1z;
 
 enum { MODE_STATS = 0, MODE_FWD = 1, MODE_REDUCE = 2, MODE_WGRAD = 3, MODE_RD = 4 };
-#ifndef TMF_C1X_ABL
-#define TMF_C1X_ABL 0              // timing ablations of the SPLIT forward (wrong results): 1 = no stores, 2 = no MFMAs
-#endif
 #ifndef TMF_C1X_LAZY
 #define TMF_C1X_LAZY 0x12          // bit MODE: the SPLIT form of that pass computes one M-tile's z at a time — the one-pass backward
                                    // needs it to stay below 256 registers (226), the forward drops to 128 (4 waves per SIMD:
@@ -47,27 +38,6 @@ enum { MODE_STATS = 0, MODE_FWD = 1, MODE_REDUCE = 2, MODE_WGRAD = 3, MODE_RD = 
 // ROUTE (fp32): the forward also keeps, per pooled window and channel, zs = the z of the first maximum and arg = its index k, and
 // MODE_RD reads (dP, zs, arg) instead of evaluating z: no MFMAs, no bf16 images, only the fp32 halo D is formed from.  The lane ->
 // window map, the brick walk and the order of every addition are those of the recomputing pass, so its slabs are the same bit for bit.
-
-// bf16 passes: the halo brick lives in LDS as bf16, TWICE — copy c stores element e at index e + c — so that the pair
-// (x[w], x[w + 1]) is one aligned dword for every w (even w: copy 0, odd w: copy 1).  A lane then fetches two taps per
-// ds_read_b32 with no conversion: 9 reads per M-tile instead of 16 fp32 reads + 8 packs.  With the fp32 halo these passes
-// were bound by the LDS port (PMC: half of all LDS cycles bank conflicts; no gather at all: 99 -> 37 us, stats, 128^3).
-// Pitches (dwords) are chosen so that the five lane bits of a fragment row land on five different address bits:
-//   w0 -> copy offset + 1 = 2 (mod 32), w1 -> 1, h0 -> 8, h1 -> 16, d0 -> 100 = 4 (mod 32): conflict-free ds_read_b32.
-constexpr int BROW = 16, BPLANE = 200;                          // elements: row, plane
-constexpr int BCP_DW = (HD * BPLANE / 2 + 1 + 31) / 32 * 32 + 1;    // copy pitch in dwords: = 1 (mod 32); TD = 4: 609 = 19 * 32 + 1
-constexpr int BCOPY = 2 * BCP_DW;                               // ... in elements
-constexpr int NHB_DW = 2 * BCP_DW;                              // dwords of LDS for both copies (copy 1 ends at 609 + 600 + 1)
-static_assert(HD * BPLANE / 2 + 1 <= BCP_DW && HH * BROW <= BPLANE && HW + 2 <= BROW, "bf16 halo layout");
-__device__ __forceinline__ constexpr int brow_off(int r) { return (r / 3) * BPLANE + (r % 3) * BROW; }   // tap row r = 3 dz + dy
-
-__device__ __forceinline__ constexpr int tapoff(int tap) {
-    return tap >= 27 ? 0 : ((tap / 9) * HH + (tap / 3) % 3) * HW + tap % 3;
-}
-// halo index (tap (0,0,0) corner) of M-tile t's origin, and of fragment row r (lane half 0) relative to it
-__device__ __forceinline__ constexpr int row_off(int r) {   // r bits: b0 -> w0, b1 -> h0, b2 -> d0, b3 -> w1
-    return (((r >> 2) & 1) * HH + ((r >> 1) & 1)) * HW + 2 * ((r >> 3) & 1) + (r & 1);
-}
 
 struct Args {
     const float* x;        // [B][D][H][W]
@@ -88,11 +58,6 @@ struct Args {
     float slope;
 };
 
-__device__ __forceinline__ tmf_bf16x8 pack8(const float (&v)[8]) {
-    const tmf_u32x4 p = {tmf_pack_bf16(v[0], v[1]), tmf_pack_bf16(v[2], v[3]), tmf_pack_bf16(v[4], v[5]), tmf_pack_bf16(v[6], v[7])};
-    return __builtin_bit_cast(tmf_bf16x8, p);
-}
-
 // BF16 = true: both products run on v_mfma_f32_32x32x16_bf16 (operands rounded to bf16, fp32 accumulation) — the
 // 27-tap convolution is 2 MFMAs instead of 14 and the tap-gradient product 2 instead of 16, which turns the four
 // passes from matrix-bound into LDS / HBM-bound (the opt-in bf16 mode of BASELINE configs[2]).
@@ -105,7 +70,7 @@ __device__ __forceinline__ tmf_bf16x8 pack8(const float (&v)[8]) {
 // routing arithmetic of these passes runs beside them instead of in between.  The fp32 halo stays next to the images for the passes
 // that multiply the inputs themselves (D of MODE_RD, the tap-gradient product of MODE_WGRAD: fp32 as before).
 template <int MODE, bool BF16, bool P16 = false, bool SPLIT = false, bool ROUTE = false>     // P16: pooled / dpool are bf16 tensors (bf16 activation storage)
-__global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT && ROUTE) ? 4 : 2) void conv1_fused_kernel(Args a) {   // <= 256 registers: MFMA results in VGPRs (no v_accvgpr_read copies)
+__global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT) ? 4 : 2) void conv1_fused_kernel(Args a) {   // <= 256 registers: MFMA results in VGPRs (no v_accvgpr_read copies)
     static_assert(!(BF16 && SPLIT), "SPLIT is the fp32 mode's variant");
     static_assert(!ROUTE || (!BF16 && !P16 && (MODE == MODE_FWD || (MODE == MODE_RD && !SPLIT))),
                   "ROUTE: the fp32 forward (either form of z) and the one-pass backward, which evaluates no z and so has one form");
@@ -127,34 +92,9 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
     const int OD = a.D / 2, OH = a.H / 2, OW = a.W / 2;
 
     float bw[B16L ? 1 : 14];
-    // BF16: K = 48 = 3 MFMAs x (2 lane halves x 4 tap rows x 2 taps): k = 16 m + 8 hsel + 2 s + t is tap row r = 4 m + s
-    // (= 3 dz + dy), dx = 2 hsel + t — the lane half picks the pair (dx 0, 1) or (dx 2, pad); rows >= 9 and dx = 3 are zero
-    tmf_bf16x8 bwb[NIMG][3];                // [part h / m / l][MFMA]
-    if (B16L) {
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = 4 * m + (j >> 1), dx = 2 * hsel + (j & 1);
-                v[j] = (r < 9 && dx < 3 && cv) ? a.w[(3 * r + dx) * a.C + co] : 0.f;
-            }
-            if (SPLIT) {
-                float vh[8], vm[8], vl[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) split3_trunc(v[j], vh[j], vm[j], vl[j]);
-                bwb[0][m] = pack8(vh); bwb[NIMG > 1 ? 1 : 0][m] = pack8(vm); bwb[NIMG > 2 ? 2 : 0][m] = pack8(vl);
-            } else {
-                bwb[0][m] = pack8(v);
-            }
-        }
-    } else if (!NOZ) {
-#pragma unroll
-        for (int s = 0; s < 14; ++s) {
-            const int tap = 2 * s + hsel;
-            bw[s] = (tap < 27 && cv) ? a.w[tap * a.C + co] : 0.f;
-        }
-    }
+    tmf_bf16x8 bwb[NIMG][3];                // [part h / m / l][MFMA]  (operand layouts: conv1_z.h)
+    if constexpr (B16L) weights_b16<SPLIT>(a.w, a.C, co, cv, hsel, bwb);
+    else if constexpr (!NOZ) weights_f32(a.w, a.C, co, cv, hsel, bw);
     float sc = 0.f, sh = 0.f, mu = 0.f, is = 0.f, c0 = 0.f, c1 = 0.f;
     if (MODE != MODE_STATS && cv) { sc = a.scale[co]; sh = a.shift[co]; }
     if ((MODE == MODE_REDUCE || MODE == MODE_WGRAD || MODE == MODE_RD) && cv) { mu = a.mean[co]; is = a.invstd[co]; }
@@ -281,26 +221,11 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
             }
             if (SPLIT) {
                 if (e < NHALO) {
-                    float ph, pm, pl;
-                    split3_trunc(hv[q], ph, pm, pl);
-                    const unsigned short p16[3] = {(unsigned short)(__builtin_bit_cast(unsigned, ph) >> 16),
-                                                   (unsigned short)(__builtin_bit_cast(unsigned, pm) >> 16),
-                                                   (unsigned short)(__builtin_bit_cast(unsigned, pl) >> 16)};
-#pragma unroll
-                    for (int im = 0; im < 3; ++im) {
-                        unsigned short* dst = reinterpret_cast<unsigned short*>(halo) + im * (2 * NHB_DW) + hdst[q];
-                        dst[0] = p16[im];
-                        dst[BCOPY + 1] = p16[im];
-                    }
+                    store_halo_split(halo, hdst[q], hv[q]);
                     if (KEEP32) halo32[e] = hv[q];
                 }
             } else if (BF16) {
-                if (e < NHALO) {
-                    const unsigned short h16 = (unsigned short)(tmf_pack_bf16(hv[q], 0.f) & 0xFFFFu);
-                    unsigned short* dst = reinterpret_cast<unsigned short*>(halo) + hdst[q];
-                    dst[0] = h16;
-                    dst[BCOPY + 1] = h16;
-                }
+                if (e < NHALO) store_halo_bf16(halo, hdst[q], hv[q]);
             } else {
                 if (e < NHALO) halo[e] = hv[q];
             }
@@ -315,95 +240,19 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
         f32x16 zt[NTI];
         constexpr bool LAZY = (BF16 && MODE == MODE_WGRAD) || (SPLIT && ((TMF_C1X_LAZY >> MODE) & 1));   // register budget: one M-tile's z at a time
         const int i = l31;
-        // BF16: A[i = voxel][k]: per MFMA four dwords = the lane half's tap pair of four tap rows (rows >= 9 repeat row 8
-        // against zero weights); the lane's byte address is loop-invariant up to the M-tile origin
-        const unsigned lane_b = hb_base + 2u * (unsigned)(((i >> 3) & 1) * BPLANE + (2 * ((i >> 2) & 1) + ((i >> 1) & 1)) * BROW +
-                                                        2 * ((i >> 4) & 1) + 2 * (i & 1) + (i & 1) * BCOPY + 2 * hsel);
-        auto load_rows = [&](int ti, unsigned (&pr)[9], int img = 0) {
-            const int mt = wave * NTI + ti;
-            const unsigned tb = lane_b + 2u * (unsigned)((2 * (mt >> 2)) * BPLANE + 4 * ((mt >> 1) & 1) * BROW + 4 * (mt & 1)) +
-                                (unsigned)(img * NHB_DW * 4);
-#pragma unroll
-            for (int r = 0; r < 9; ++r)
-                pr[r] = *reinterpret_cast<const __attribute__((address_space(3))) unsigned*>((size_t)(tb + 2u * (unsigned)brow_off(r)));
+        const unsigned lane_b = lane_base(hb_base, i, hsel);
+        // one M-tile's z (LAZY), or all of the wave's with their chains interleaved: conv1_z.h, the same products in the same order
+        auto conv_tiles = [&](f32x16* zp, int mt0, auto n_c) {
+            constexpr int N = decltype(n_c)::value;
+            if constexpr (B16L) conv_tiles_b16<SPLIT, N>(zp, lane_b, mt0, bwb);
+            else conv_tiles_f32<N>(zp, halo, mt0, vox_off(i), hsel, bw);
         };
-        auto mma = [&](int ti, int m, const unsigned (&pr)[9], int wpart = 0) {
-            const tmf_u32x4 av = {pr[4 * m < 9 ? 4 * m : 8], pr[4 * m + 1 < 9 ? 4 * m + 1 : 8],
-                              pr[4 * m + 2 < 9 ? 4 * m + 2 : 8], pr[4 * m + 3 < 9 ? 4 * m + 3 : 8]};
-#if TMF_C1X_ABL & 2
-            asm volatile("" :: "v"(av));
-            zt[ti][m] += __builtin_bit_cast(float, av[0]);
-#else
-            zt[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tmf_bf16x8, av), bwb[wpart < NIMG ? wpart : 0][m], zt[ti], 0, 0, 0);
-#endif
-        };
-        auto conv_one = [&](int ti) {
-            unsigned pr[9];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zt[ti][r] = 0.f;
-            if (SPLIT) {                                    // (the order of the interleaved form below: bit-identical z)
-#pragma unroll
-                for (int img = 2; img >= 0; --img) {
-                    load_rows(ti, pr, img);
-#pragma unroll
-                    for (int wp = 2 - img; wp >= 0; --wp)
-#pragma unroll
-                        for (int m = 0; m < 3; ++m) mma(ti, m, pr, wp);
-                }
-                return;
-            }
-            load_rows(ti, pr);
-#pragma unroll
-            for (int m = 0; m < 3; ++m) mma(ti, m, pr);
-        };
-        if (!LAZY && !NOZ) {
-            const int vox = (((i >> 3) & 1) * HH + 2 * ((i >> 2) & 1) + ((i >> 1) & 1)) * HW + 2 * ((i >> 4) & 1) + (i & 1);
-            int a_vox[NTI];
-#pragma unroll
-            for (int ti = 0; ti < NTI; ++ti) {
-                const int mt = wave * NTI + ti;
-                a_vox[ti] = ((2 * (mt >> 2)) * HH + 4 * ((mt >> 1) & 1)) * HW + 4 * (mt & 1) + vox;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) zt[ti][r] = 0.f;
-            }
-            if (SPLIT) {
-                // image l, then m, then h — the products in ascending size: wh xl | wm xm, wh xm | wl xh, wm xh, wh xh
-#pragma unroll
-                for (int img = 2; img >= 0; --img) {
-                    unsigned pr[NTI][9];
-#pragma unroll
-                    for (int ti = 0; ti < NTI; ++ti) load_rows(ti, pr[ti], img);
-#pragma unroll
-                    for (int wp = 2 - img; wp >= 0; --wp)
-#pragma unroll
-                        for (int m = 0; m < 3; ++m)
-#pragma unroll
-                            for (int ti = 0; ti < NTI; ++ti) mma(ti, m, pr[ti], wp);
-                }
-            } else if (BF16) {
-                unsigned pr[NTI][9];
-#pragma unroll
-                for (int ti = 0; ti < NTI; ++ti) load_rows(ti, pr[ti]);
-#pragma unroll
-                for (int m = 0; m < 3; ++m) {
-#pragma unroll
-                    for (int ti = 0; ti < NTI; ++ti) mma(ti, m, pr[ti]);
-                }
-            } else {
-#pragma unroll
-                for (int s = 0; s < 14; ++s) {
-                    const int off = hsel ? tapoff(2 * s + 1) : tapoff(2 * s);
-#pragma unroll
-                    for (int ti = 0; ti < NTI; ++ti)
-                        zt[ti] = __builtin_amdgcn_mfma_f32_32x32x2f32(halo[a_vox[ti] + off], bw[s], zt[ti], 0, 0, 0);
-                }
-            }
-        }
+        if (!LAZY && !NOZ) conv_tiles(zt, wave * NTI, std::integral_constant<int, NTI>{});
 #pragma unroll
         for (int ti = 0; ti < NTI; ++ti) {
             const int mt = wave * NTI + ti;                     // M-tile of the brick (wave-uniform)
-            const int org = ((2 * (mt >> 2)) * HH + 4 * ((mt >> 1) & 1)) * HW + 4 * (mt & 1);
-            if (LAZY) conv_one(ti);
+            const int org = tile_org(mt);
+            if (LAZY) conv_tiles(&zt[ti], mt, std::integral_constant<int, 1>{});
             f32x16& z = zt[ti];
             // voxel coordinates of this lane's 16 rows (row r, lane half hsel), relative to the brick:
             //   d = 2*(mt>>2) + r[2],  h = 4*((mt>>1)&1) + 2*hsel + r[1],  w = 4*(mt&1) + 2*r[3] + r[0]
@@ -460,9 +309,8 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
                     continue;
                 }
                 float y[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) y[k] = z[8 * q + k] * sc + sh;
-                const float ymax = fmaxf(fmaxf(fmaxf(y[0], y[1]), fmaxf(y[2], y[3])), fmaxf(fmaxf(y[4], y[5]), fmaxf(y[6], y[7])));
+                window_y(z, q, sc, sh, y);
+                const float ymax = window_max(y);
                 const float lrm = ymax > 0.f ? 1.f : a.slope;
                 if (MODE == MODE_FWD) {
                     const float best = ymax * lrm;
@@ -471,14 +319,8 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
                         if (P16) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(tmf_pack_bf16(best, 0.f) & 0xFFFFu), pr, pv, psoff, 0);
                         else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, best), pr, pv, psoff, 0);
                         if (ROUTE) {                            // the routing MODE_RD derives: the FIRST k with y[k] == ymax
-                            float zs = z[8 * q + 7];
-                            int arg = 7;
-#pragma unroll
-                            for (int k = 6; k >= 0; --k) {
-                                const bool hit = y[k] == ymax;
-                                zs = hit ? z[8 * q + k] : zs;
-                                arg = hit ? k : arg;
-                            }
+                            const float zs = window_zsel(y, ymax, z, q);
+                            const int arg = window_arg(y, ymax);
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, zs), zr, pv, psoff, 0);
                             __builtin_amdgcn_raw_buffer_store_b8((unsigned char)arg, ar, (int)((unsigned)pv >> 2), psoff / PSZ, 0);
                         }
@@ -491,16 +333,12 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
                             : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr, pv, psoff, 0));
                 const float gl = g * lrm;                       // dLoss/dy at the routed element
                 if (MODE == MODE_REDUCE || MODE == MODE_RD) {
-                    float zs = z[8 * q + 7];                    // z of the first maximum (a pooled window is all-valid)
-#pragma unroll
-                    for (int k = 6; k >= 0; --k) zs = (y[k] == ymax) ? z[8 * q + k] : zs;
+                    const float zs = window_zsel(y, ymax, z, q);   // z of the first maximum (a pooled window is all-valid)
                     s1 += gl;
                     s2 += gl * ((zs - mu) * is);
                     if (MODE == MODE_RD) {
                         // the routed voxel's 27 input taps (halo index of fragment row r = 8 q + k: row_off(r) + the lane half's rows)
-                        int arg = 7;
-#pragma unroll
-                        for (int k = 6; k >= 0; --k) arg = (y[k] == ymax) ? k : arg;
+                        const int arg = window_arg(y, ymax);
                         if (BF16) {
                             // the bf16 halo (copy 0: element index = hd * BPLANE + hh * BROW + hw): the inputs as the MFMAs of z saw them
                             const int hd = 2 * (mt >> 2) + ((arg >> 2) & 1), hh = 4 * ((mt >> 1) & 1) + 2 * hsel + ((arg >> 1) & 1);
@@ -519,9 +357,7 @@ __global__ __launch_bounds__(256, (MODE == 3 && !SPLIT) || (MODE == 1 && SPLIT &
                         }
                     }
                 } else {
-                    int arg = 7;
-#pragma unroll
-                    for (int k = 6; k >= 0; --k) arg = (y[k] == ymax) ? k : arg;
+                    const int arg = window_arg(y, ymax);
                     const float add = sc * gl;
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
@@ -635,12 +471,7 @@ Plan make_plan(int B, int D, int H, int W, int C, int target_blocks) {
 // against 0.796 at 8 per CU and 0.81 at 14-20; TMF_C1_BLOCKS overrides); FWD has no slab.
 #define SLAB_BLOCKS tmf_opt(TMF_OPT_C1_BLOCKS)
 
-int check(const char* fn, int B, int D, int H, int W, int C) {
-    TMF_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && C > 0, TMF_E_SHAPE, "%s: non-positive dimension", fn);
-    TMF_REQUIRE((long)D * H * W * C < (1L << 31), TMF_E_SHAPE, "%s: one sample exceeds 2^31 elements", fn);
-    TMF_REQUIRE((long)(D > 6 ? D : 6) * H * W < (1L << 29), TMF_E_SHAPE, "%s: the input volume exceeds 2^29 voxels", fn);
-    return TMF_OK;
-}
+int check(const char* fn, int B, int D, int H, int W, int C) { return check_shape(fn, B, D, H, W, C); }     // (conv1_z.h)
 
 Args base_args(const float* x, const float* w, int D, int H, int W, int C, const Plan& p, float slope) {
     Args a = {};
@@ -801,7 +632,7 @@ extern "C" int tmf_c1_bwd_wgrad_bf16(const float* x, const float* w, const float
 // workspace: [nblk][2][C] sums | [nblk][27][C] D slabs | their reduction scratch | [27][C] reduced D
 int tmf_c1_bwd_fused_finish(const float* part, int nblk, const float* dred, const float* w, const void* gram, const float* scale,
                             const float* mean, const float* invstd, double count, float* dgamma, float* dbeta, float* dw, int C,
-                            int dw_ref, int round16, void* stream);
+                            int dw_ref, int round16, void* stream, float* coef);
 extern "C" size_t tmf_c1_bwd_fused_workspace_bytes(int B, int D, int H, int W, int C) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
     const Plan p = make_plan(B, D, H, W, C, SLAB_BLOCKS);
@@ -810,7 +641,8 @@ extern "C" size_t tmf_c1_bwd_fused_workspace_bytes(int B, int D, int H, int W, i
 static int c1_bwd_fused(bool bf16, bool p16, const float* x, const float* w, const float* scale, const float* shift, const float* mean,
                         const float* invstd, const void* dpool, const void* gram, float* dw, float* dgamma, float* dbeta,
                         void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int C, float slope,
-                        int dw_layout, void* stream, const float* z_sel = nullptr, const unsigned char* arg = nullptr) {
+                        int dw_layout, void* stream, const float* z_sel = nullptr, const unsigned char* arg = nullptr,
+                        float* coef = nullptr) {
     TMF_REQUIRE(dw_layout == TMF_DW_TAPMAJOR || dw_layout == TMF_DW_REFERENCE, TMF_E_ARG, "tmf_c1_bwd_fused: unknown dw_layout %d", dw_layout);
     TMF_REQUIRE_PTR(x); TMF_REQUIRE_PTR(w); TMF_REQUIRE_PTR(scale); TMF_REQUIRE_PTR(shift); TMF_REQUIRE_PTR(mean); TMF_REQUIRE_PTR(invstd);
     TMF_REQUIRE_PTR(dpool); TMF_REQUIRE_PTR(gram); TMF_REQUIRE_PTR(dw); TMF_REQUIRE_PTR(workspace);
@@ -839,7 +671,7 @@ static int c1_bwd_fused(bool bf16, bool p16, const float* x, const float* w, con
     if ((rc = tmf_launch_result("tmf_c1_bwd_fused"))) return rc;
     if ((rc = tmf_reduce_slabs(slabs, p.nblk, n, scratch, dred, s, "tmf_c1_bwd_fused(reduce)"))) return rc;
     return tmf_c1_bwd_fused_finish(part, p.nblk, dred, w, gram, scale, mean, invstd, (double)B * D * H * W, dgamma, dbeta, dw, C,
-                                   dw_layout == TMF_DW_REFERENCE ? 1 : 0, bf16 ? 1 : 0, stream);
+                                   dw_layout == TMF_DW_REFERENCE ? 1 : 0, bf16 ? 1 : 0, stream, coef);
 }
 extern "C" int tmf_c1_bwd_fused(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
                                 const float* invstd, const float* dpool, const void* gram, float* dw, float* dgamma, float* dbeta,
@@ -856,6 +688,17 @@ extern "C" int tmf_c1_bwd_fused_route(const float* x, const float* w, const floa
     TMF_REQUIRE_PTR(z_sel); TMF_REQUIRE_PTR(arg);
     return c1_bwd_fused(false, false, x, w, scale, shift, mean, invstd, dpool, gram, dw, dgamma, dbeta, workspace, workspace_bytes,
                         B, D, H, W, C, slope, dw_layout, stream, z_sel, arg);
+}
+// ... and additionally coef [2][C] = (sum dy, sum dy xhat) / count from the finish kernel's doubles, for tmf_c1_bwd_dgrad; dw, dgamma and
+// dbeta are those of the entries above bit for bit.  z_sel / arg may both be NULL (the recomputing form).
+extern "C" int tmf_c1_bwd_fused_coef(const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                                     const float* invstd, const float* dpool, const float* z_sel, const unsigned char* arg,
+                                     const void* gram, float* dw, float* dgamma, float* dbeta, float* coef, void* workspace,
+                                     size_t workspace_bytes, int B, int D, int H, int W, int C, float slope, int dw_layout, void* stream) {
+    TMF_REQUIRE_PTR(coef);
+    TMF_REQUIRE((z_sel == nullptr) == (arg == nullptr), TMF_E_NULL, "tmf_c1_bwd_fused_coef: z_sel and arg go together");
+    return c1_bwd_fused(false, false, x, w, scale, shift, mean, invstd, dpool, gram, dw, dgamma, dbeta, workspace, workspace_bytes,
+                        B, D, H, W, C, slope, dw_layout, stream, z_sel, arg, coef);
 }
 // the bf16 mode's form (gram from tmf_c1_stats_g_bf16): z and D from the volume and the taps rounded to bf16, dy unrounded — the
 // weight gradient is that of the bf16 forward WITHOUT the second rounding of dz that tmf_c1_bwd_wgrad_bf16's product performs

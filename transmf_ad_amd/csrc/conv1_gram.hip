@@ -315,7 +315,8 @@ __global__ __launch_bounds__(1024) void c1_bwd_fused_finish_kernel(const float* 
                                                                     const float* __restrict__ scale, const float* __restrict__ mean,
                                                                     const float* __restrict__ invstd, double count,
                                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                    float* __restrict__ dw, int C, int dw_ref, int round16) {
+                                                                    float* __restrict__ dw, int C, int dw_ref, int round16,
+                                                                    float* __restrict__ coef) {
     __shared__ double pa[16 * 2 * GMAXC];
     __shared__ double c01[2 * GMAXC];
     __shared__ float wsh[27 * GMAXC];
@@ -334,6 +335,7 @@ __global__ __launch_bounds__(1024) void c1_bwd_fused_finish_kernel(const float* 
 #pragma unroll
         for (int rg = 0; rg < 16; ++rg) s += pa[rg * 2 * C + j];
         c01[j] = s / count;
+        if (coef) coef[j] = (float)c01[j];                          // [2][C]: what tmf_bn_bwd_finalize hands the data-gradient pass
         if (j < C) { if (dbeta) dbeta[j] = (float)s; }
         else if (dgamma) dgamma[j - C] = (float)s;
     }
@@ -401,8 +403,8 @@ extern "C" int tmf_c1_stats_g_bf16(const float* x, const float* w, float* stat_p
 
 int tmf_c1_bwd_fused_finish(const float* part, int nblk, const float* dred, const float* w, const void* gram, const float* scale,
                             const float* mean, const float* invstd, double count, float* dgamma, float* dbeta, float* dw, int C,
-                            int dw_ref, int round16, void* stream) {
+                            int dw_ref, int round16, void* stream, float* coef) {
     hipLaunchKernelGGL(c1_bwd_fused_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, nblk, dred, w, (const double*)gram,
-                       scale, mean, invstd, count, dgamma, dbeta, dw, C, dw_ref, round16);
+                       scale, mean, invstd, count, dgamma, dbeta, dw, C, dw_ref, round16, coef);
     return tmf_launch_result("tmf_c1_bwd_fused(finish)");
 }

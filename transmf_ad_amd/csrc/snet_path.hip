@@ -41,6 +41,7 @@ struct Plan {
     size_t saved_bytes;
     // backward scratch
     size_t off_bpart, off_coef, off_dz, off_gA, off_gB, off_ws, scratch_bytes, ws_bytes;
+    size_t off_dgws, dgws_bytes;                // the first block's data gradient (tmf_snet_train_bwd_input): its prepared coefficients
 };
 
 int check_desc(const char* fn, const tmf_snet_desc* d) {
@@ -146,6 +147,8 @@ Plan make_plan(const tmf_snet_desc& d, bool train = true) {
     p.off_gB = so; so += up256(x_max);
     p.off_ws = so; so += up256(ws_max > 16 ? ws_max : 16);
     p.ws_bytes = ws_max > 16 ? ws_max : 16;
+    p.dgws_bytes = tmf_c1_bwd_dgrad_workspace_bytes(d.B, p.L[0].D, p.L[0].H, p.L[0].W, p.L[0].cout);
+    p.off_dgws = so; so += up256(p.dgws_bytes);
     p.scratch_bytes = so;
     return p;
 }
@@ -338,10 +341,15 @@ extern "C" int tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const
     return TMF_OK;
 }
 
-extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, const void* saved, size_t saved_bytes,
-                                  const float* dout, const tmf_snet_grads* g, void* scratch, size_t scratch_bytes,
-                                  void* stream) {
+// dvol != NULL: block 0 additionally runs the data-gradient pass (conv1_dgrad.hip) on block 1's data gradient; NULL: exactly the
+// launches of tmf_snet_train_bwd.  (Error messages name tmf_snet_train_bwd for both.)
+extern "C" int tmf_snet_train_bwd_input(const tmf_snet_desc* d, const float* vol, const void* saved, size_t saved_bytes,
+                                        const float* dout, const tmf_snet_grads* g, void* scratch, size_t scratch_bytes,
+                                        void* stream, float* dvol) {
     TMF_TRY(check_desc("tmf_snet_train_bwd", d));
+    TMF_REQUIRE(dvol == nullptr || d->precision != TMF_PREC_BF16, TMF_E_ARG,
+                "tmf_snet_train_bwd_input: the input gradient needs the fp32 or fp32x precision");
+    if (dvol != nullptr) TMF_REQUIRE_ALIGNED(dvol);
     const TmfAlgoScope algo_scope(d->flags);          // (the forward's: the plan of `saved` is the one the forward laid out)
     TMF_REQUIRE_PTR(vol); TMF_REQUIRE_PTR(saved); TMF_REQUIRE_PTR(dout); TMF_REQUIRE_PTR(g); TMF_REQUIRE_PTR(scratch);
     TMF_REQUIRE_ALIGNED(vol); TMF_REQUIRE_ALIGNED(saved); TMF_REQUIRE_ALIGNED(dout); TMF_REQUIRE_ALIGNED(scratch);
@@ -392,9 +400,19 @@ extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, cons
             hipError_t e = hipMemsetAsync(g->dbias[l], 0, (size_t)L.cout * 4, s);
             TMF_REQUIRE(e == hipSuccess, (int)e, "tmf_snet_train_bwd: memset failed: %s", hipGetErrorString(e));
         }
-        if ((size_t)L.oD * L.oH * L.oW == 0) continue;
+        if ((size_t)L.oD * L.oH * L.oW == 0) continue;       // (never block 0: check_desc wants every edge >= 16, so dvol is always written)
         if (l == 0 && p.c1gram_bytes && g->dweight[l] != nullptr) {
             // one pass over the volume: BatchNorm sums and D = x (*) dy together; dw from the forward's Gram data (conv1_gram.hip)
+            if (dvol != nullptr) {                          // ... which then also hands out coef for the data gradient
+                TMF_TRY(tmf_c1_bwd_fused_coef(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, (const float*)go,
+                                              L.route ? (const float*)(base + L.off_zsel) : nullptr,
+                                              L.route ? (const unsigned char*)(base + L.off_arg) : nullptr, base + p.off_c1gram,
+                                              g->dweight[l], g->dgamma[l], g->dbeta[l], coef, ws, p.ws_bytes, d->B, L.D, L.H, L.W, L.cout,
+                                              d->slope[l], TMF_DW_REFERENCE, stream));
+                TMF_TRY(tmf_c1_bwd_dgrad(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, coef, (const float*)go, dvol,
+                                         sc + p.off_dgws, p.dgws_bytes, d->B, L.D, L.H, L.W, L.cout, d->slope[l], stream));
+                break;
+            }
             if (b16) TMF_TRY(tmf_c1_bwd_fused_bf16(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, go, base + p.off_c1gram,
                                                    g->dweight[l], g->dgamma[l], g->dbeta[l], ws, p.ws_bytes, d->B, L.D, L.H, L.W, L.cout,
                                                    d->slope[l], L.o16 ? 1 : 0, TMF_DW_REFERENCE, stream));
@@ -422,6 +440,9 @@ extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, cons
                                                   (const float*)go, g->dweight[l], ws, p.ws_bytes, d->B, L.D, L.H, L.W, L.cout,
                                                   d->slope[l], TMF_DW_REFERENCE, stream));
             }
+            if (dvol != nullptr)
+                TMF_TRY(tmf_c1_bwd_dgrad(vol, (const float*)wf, v.scale, v.shift, v.mean, v.invstd, coef, (const float*)go, dvol,
+                                         sc + p.off_dgws, p.dgws_bytes, d->B, L.D, L.H, L.W, L.cout, d->slope[l], stream));
             break;
         }
         const int io = (L.z16 ? 1 : 0) | (L.o16 ? 2 : 0);
@@ -460,4 +481,10 @@ extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, cons
         }
     }
     return TMF_OK;
+}
+
+extern "C" int tmf_snet_train_bwd(const tmf_snet_desc* d, const float* vol, const void* saved, size_t saved_bytes,
+                                  const float* dout, const tmf_snet_grads* g, void* scratch, size_t scratch_bytes,
+                                  void* stream) {
+    return tmf_snet_train_bwd_input(d, vol, saved, saved_bytes, dout, g, scratch, scratch_bytes, stream, nullptr);
 }

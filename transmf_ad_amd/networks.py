@@ -137,9 +137,12 @@ class sNet(nn.Module):
         return x                                 # (B, d, h, w, dim)
 
     def _one_call_ok(self, vol, blocks, eval_mode=False, prec=None):
-        """Train-mode batch statistics in every block, the standard sNet(dim) geometry, no gradient wanted for the
-        input: the whole pass is one library call (ops.SNetTrain); anything else goes block by block."""
-        if vol.requires_grad or not vol.is_cuda or vol.dtype != torch.float32:
+        """Train-mode batch statistics in every block and the standard sNet(dim) geometry: the whole pass is one library call
+        (ops.SNetTrain); anything else goes block by block.  An input that wants a gradient stays on the one call in the
+        fp32 / fp32x precisions (tmf_snet_train_bwd_input); the bf16 precision has no first-block data gradient."""
+        if not vol.is_cuda or vol.dtype != torch.float32:
+            return False
+        if vol.requires_grad and (eval_mode or ops.resolve_precision(prec)[0] == "bf16"):
             return False
         B, _, D, H, W = vol.shape
         dim = blocks[-1][0].out_channels

@@ -9,6 +9,7 @@ from __future__ import annotations
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -448,7 +449,7 @@ class ConvBnActPool(torch.autograd.Function):
 
 class Conv1BnPool(torch.autograd.Function):
     """First sNet block (Cin = 1, 3x3x3, max pool) with the conv output never written to HBM: the statistics,
-    forward, backward-reduce and weight-gradient passes each recompute it from the input volume."""
+    forward, backward-reduce, weight-gradient and data-gradient passes each recompute it from the input volume."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, training, momentum, eps, slope,
@@ -499,9 +500,12 @@ class Conv1BnPool(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         x, wp, scale, shift, mean, invstd = ctx.saved_tensors
         training, slope, C, has_bias, sfx, p16 = ctx.cfg
+        if ctx.needs_input_grad[0] and sfx:
+            raise _lib.TmfError("the fused first block has no data gradient in the bf16 precision")
         B, D, H, W, _ = x.shape
         dev = x.device
         s = _stream()
@@ -509,18 +513,35 @@ class Conv1BnPool(torch.autograd.Function):
         want16 = bool(p16 and p16[0])
         if (dout.dtype == _b16) != want16:
             dout = dout.to(_b16 if want16 else _f32)
-        if ctx.gram is not None and training and ctx.needs_input_grad[1] and not ctx.needs_input_grad[0]:
+        def dgrad(coef):       # the data gradient from coef = (sum dy, sum dy xhat) / count (zeros: eval mode), conv1_dgrad.hip
+            nb = _lib.query("tmf_c1_bwd_dgrad_workspace_bytes", B, D, H, W, C)
+            dws = torch.empty((max(nb, 16) // 4,), device=dev, dtype=_f32)
+            dx = torch.empty(x.shape, device=dev, dtype=_f32)
+            _lib.call("tmf_c1_bwd_dgrad", x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                      invstd.data_ptr(), coef.data_ptr(), dout.data_ptr() if dout.numel() else None, dx.data_ptr(), dws.data_ptr(), nb,
+                      B, D, H, W, C, slope, s)
+            return dx
+
+        if ctx.gram is not None and training and ctx.needs_input_grad[1]:
             # one pass over the volume: BatchNorm sums and D = x (*) dy together, dw from the forward's Gram data
             nbytes = _lib.query("tmf_c1_bwd_fused_workspace_bytes", B, D, H, W, C)
             ws = torch.empty((max(nbytes, 16) // 4,), device=dev, dtype=_f32)
             dweight = torch.empty((C, 1, 3, 3, 3), device=dev, dtype=_f32)
             dgamma = torch.empty(C, device=dev, dtype=_f32)
             dbeta = torch.empty(C, device=dev, dtype=_f32)
-            _lib.call("tmf_c1_bwd_fused" + sfx, x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                      invstd.data_ptr(), dout.data_ptr(), ctx.gram.data_ptr(), dweight.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                      ws.data_ptr(), nbytes, B, D, H, W, C, slope, *p16, _lib.DW_REFERENCE, s)
+            dx = None
+            if ctx.needs_input_grad[0]:    # the same pass also hands out coef (from the finish kernel's doubles); dw, dgamma, dbeta unchanged
+                coef = torch.empty((2, C), device=dev, dtype=_f32)
+                _lib.call("tmf_c1_bwd_fused_coef", x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                          invstd.data_ptr(), dout.data_ptr(), None, None, ctx.gram.data_ptr(), dweight.data_ptr(), dgamma.data_ptr(),
+                          dbeta.data_ptr(), coef.data_ptr(), ws.data_ptr(), nbytes, B, D, H, W, C, slope, _lib.DW_REFERENCE, s)
+                dx = dgrad(coef)
+            else:
+                _lib.call("tmf_c1_bwd_fused" + sfx, x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                          invstd.data_ptr(), dout.data_ptr(), ctx.gram.data_ptr(), dweight.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                          ws.data_ptr(), nbytes, B, D, H, W, C, slope, *p16, _lib.DW_REFERENCE, s)
             dbias = torch.zeros(C, device=dev, dtype=_f32) if has_bias else None
-            return (None, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None)
+            return (dx, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None)
         nblk = _lib.query("tmf_c1_blocks", B, D, H, W, C)
         part = torch.empty((nblk, 2, C), device=dev, dtype=_f32)
         _lib.call("tmf_c1_bwd_reduce" + sfx, x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(),
@@ -543,9 +564,8 @@ class Conv1BnPool(torch.autograd.Function):
             _lib.call("tmf_c1_bwd_wgrad" + sfx, x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                       mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(), dout.data_ptr(), dweight.data_ptr(),
                       ws.data_ptr(), nbytes, B, D, H, W, C, slope, *p16, _lib.DW_REFERENCE, s)
-        if ctx.needs_input_grad[0]:
-            raise _lib.TmfError("the fused first block has no data gradient (the network input needs none)")
-        return (None, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None)
+        dx = dgrad(coef) if ctx.needs_input_grad[0] else None
+        return (dx, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None)
 
 
 def conv_bn_act_pool_eval_fused(x, weight, bias, gamma, beta, running_mean, running_var, eps, slope, pool):
@@ -587,7 +607,10 @@ def conv_bn_act_pool(x, weight, bias, gamma, beta, running_mean, running_var, tr
     if (FUSE_EVAL_BLOCKS and not training and not needs_graph and mode == "fp32" and weight.shape[1] > 1
             and weight.shape[1] % 4 == 0 and weight.shape[0] % 4 == 0):
         return conv_bn_act_pool_eval_fused(x, weight, bias, gamma, beta, running_mean, running_var, eps, slope, pool)
-    if (weight.shape[1] == 1 and weight.shape[2] == 3 and pool == "max" and not x.requires_grad):
+    # (an input that wants a gradient: the fused block has the data-gradient pass in the fp32 precisions; the bf16 precision, and a
+    # bf16 output asked of an fp32 block, keep the generic route)
+    if (weight.shape[1] == 1 and weight.shape[2] == 3 and pool == "max"
+            and (not x.requires_grad or (mode != "bf16" and not out_bf16))):
         if out_bf16 and mode != "bf16":
             raise _lib.TmfError("a bf16 block output needs conv precision 'bf16'")
         return Conv1BnPool.apply(x, weight, bias, gamma, beta, running_mean, running_var,
@@ -706,7 +729,7 @@ class SNetTrain(torch.autograd.Function):
         B, _, D, H, W = vol.shape
         desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision={"fp32": 0, "bf16": 1, "fp32x": 2}[mode], storage_bf16=int(act16),
                              flags=(_lib.SNET_ALONE if (len(cfg) > 5 and cfg[5]) else 0) | snet_algo_flags(cfg[6] if len(cfg) > 6 else None))
-        if not any(ctx.needs_input_grad[3:]):
+        if not any(ctx.needs_input_grad):
             desc.flags |= 0x30000              # no backward will follow (no_grad, frozen encoder): keep no pool routing in `saved`
         prm = _lib.SnetParams()
         for l in range(7):
@@ -760,21 +783,26 @@ class SNetTrain(torch.autograd.Function):
         return flat, grads, g, ev, o_deep
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         import ctypes as C
         vol, saved = ctx.saved_tensors
         desc = ctx.desc
-        if ctx.needs_input_grad[0]:
-            raise _lib.TmfError("the one-call sNet has no data gradient (the network input needs none)")
         dout = _chk(dout, "grad_output")
         prep = ctx.bwd if ctx.bwd is not None else SNetTrain._prepare_backward(ctx.shapes, ctx.needs_input_grad, vol.device)
         ctx.bwd = None
         flat, grads, g, ev, o_deep = prep
         nscr = _lib.query("tmf_snet_bwd_scratch_bytes", C.byref(desc))
         scratch = torch.empty(nscr, device=vol.device, dtype=torch.uint8)
-        _lib.call("tmf_snet_train_bwd", C.byref(desc), vol.data_ptr(), saved.data_ptr(), saved.numel(), dout.data_ptr(),
-                  C.byref(g), scratch.data_ptr(), nscr, _stream())
-        out = [None, None, None]
+        dvol = None
+        if ctx.needs_input_grad[0]:        # block 0 also runs the data-gradient pass (fp32 / fp32x; the library refuses bf16)
+            dvol = torch.empty_like(vol)
+            _lib.call("tmf_snet_train_bwd_input", C.byref(desc), vol.data_ptr(), saved.data_ptr(), saved.numel(), dout.data_ptr(),
+                      C.byref(g), scratch.data_ptr(), nscr, _stream(), dvol.data_ptr())
+        else:
+            _lib.call("tmf_snet_train_bwd", C.byref(desc), vol.data_ptr(), saved.data_ptr(), saved.numel(), dout.data_ptr(),
+                      C.byref(g), scratch.data_ptr(), nscr, _stream())
+        out = [dvol, None, None]
         for i, gr in enumerate(grads):
             out.append(gr if (gr is not None and ctx.needs_input_grad[3 + i]) else None)
         if _FLAT_GRAD_CONSUMERS and all(ctx.needs_input_grad[3 + i] for i, gr in enumerate(grads) if gr is not None):
