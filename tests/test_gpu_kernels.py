@@ -291,12 +291,36 @@ EVAL_EXTRA = [
 ]
 
 
-@pytest.mark.parametrize("case", BLOCK_CASES + EVAL_EXTRA)
-def test_eval_block_single_pass(case):
+def _winograd_takes(case):
+    """At conv_wino >= 2 the block's fused eval form is tmf_conv3d_fwd_wino_affine, not the direct kernel's epilogue."""
+    B, D, H, W, cin, cout, k, pool = case
+    return k == 3 and cin % 8 == 0 and cout % 32 == 0 and pool != "avg"
+
+
+# Every case at the default conv_wino 3 (ids case0, case1, ... as before); the cases Winograd takes there once more at
+# conv_wino 0, on tmf_conv3d_fwd_affine — but for the two batch-8 ones, whose brick geometries tests/test_gpu_conv_variants.py
+# runs at a fraction of the size.  (The other cases run the same kernels under either setting.)
+EVAL_CASES = [pytest.param(c, 3, id="case{}".format(i)) for i, c in enumerate(BLOCK_CASES + EVAL_EXTRA)] + [
+    pytest.param(c, 0, id="case{}-direct".format(i)) for i, c in enumerate(BLOCK_CASES + EVAL_EXTRA) if _winograd_takes(c) and c[0] != 8]
+
+
+@pytest.fixture
+def conv_wino(request):
+    from transmf_ad_amd import _lib
+    _lib.call("tmf_set_option", b"conv_wino", request.param)
+    yield request.param
+    _lib.call("tmf_set_option", b"conv_wino", 3)
+
+
+@pytest.mark.parametrize("case,conv_wino", EVAL_CASES, indirect=["conv_wino"])
+def test_eval_block_single_pass(case, conv_wino):
     """Inference form (no_grad, eval): conv + folded BN + LeakyReLU + pool in one kernel, against fp64 on the host
     and against the two-pass path on the same data."""
     ops = _ops()
     B, D, H, W, cin, cout, k, pool = case
+    assert ops.conv_wino_mode() == conv_wino
+    if conv_wino == 0:
+        assert ops.wino_ok(cin, cout)             # a case the default setting sends to the Winograd kernel
     if cin == 1 or cin % 4 or cout % 4:
         pytest.skip("single-pass eval kernel needs cin > 1 and channel counts that are multiples of 4")
     x = _rand(B, cin, D, H, W, seed=141)
