@@ -52,10 +52,12 @@ class Arena:
     def ptr(self, name):
         return self.base + self.slots[name][0]
 
-    def fetch(self, may_nan=(), workspace=()):
+    def fetch(self, may_nan=(), workspace=(), written=None):
         """Synchronise, check the bytes outside the outputs, return {output name: host tensor}.  `may_nan`: outputs whose
         values may be NaN by computation (they must still be fully written: no element keeps the fill pattern, which no
-        arithmetic produces); `workspace`: scratch slots - their surroundings are checked, their content is not judged."""
+        arithmetic produces); `workspace`: scratch slots - their surroundings are checked, their content is not judged;
+        `written`: {output name: bool tensor of its shape} for an output that is a strided block of its slot - the elements
+        marked False must keep the fill pattern, the checks above apply to the others."""
         torch.cuda.synchronize()
         back = self.dev.cpu()
         at = 0
@@ -70,11 +72,18 @@ class Arena:
             res[name] = back[off:off + n].view(dtype).view(shape)
             if name in workspace:
                 continue
-            if name in may_nan or not dtype.is_floating_point:
+            live = written.get(name) if written else None
+            if live is not None or name in may_nan or not dtype.is_floating_point:
                 word = {2: torch.int16, 4: torch.int32}[torch.empty(0, dtype=dtype).element_size()]
-                assert not bool((back[off:off + n].view(word) == -1).any()), f"'{name}' holds unwritten elements"
+                fill = back[off:off + n].view(word).view(shape) == -1
+            if live is None:
+                live = ...
             else:
-                assert not torch.isnan(res[name]).any(), f"'{name}' holds NaN (unwritten or computed)"
+                assert bool(fill[~live].all()), f"'{name}': elements outside the output block were written"
+            if name in may_nan or not dtype.is_floating_point:
+                assert not bool(fill[live].any()), f"'{name}' holds unwritten elements"
+            else:
+                assert not torch.isnan(res[name][live]).any(), f"'{name}' holds NaN (unwritten or computed)"
         return res
 
 

@@ -279,10 +279,12 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dq_kernel(
                 for (int r = 0; r < 16; ++r) { sT[r] = 0.f; dpT[r] = 0.f; }
                 mma_rows<DH>(sT, Ks, kt * 32, qreg, l31, hsel);
                 mma_rows<DH>(dpT, Vs, kt * 32, doreg, l31, hsel);
-                // zero-filled key rows give dS * 0 below, so no key mask is needed here
+                // a zero-filled key row has s = 0: exp2f(0 - lse2) overflows for a row whose scores all lie far below zero,
+                // and inf * 0 against the zero K row would be NaN - so p = 0 there, as in the forward
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float p = exp2f(sT[r] - lse2);
+                    const int key = sb0 + kt * 32 + frag_row(r, hsel);
+                    const float p = key < M ? exp2f(sT[r] - lse2) : 0.f;
                     sT[r] = p * (dpT[r] - delta) * scale;
                 }
 #pragma unroll
@@ -565,6 +567,7 @@ extern "C" int tmf_xattn_bwd(const float* q, const float* k, const float* v, con
     TMF_REQUIRE(dkv_stride >= heads * dh && dkv_stride % 4 == 0 && (heads * dh) % 4 == 0, TMF_E_SHAPE,
                 "tmf_xattn_bwd: dkv_stride must be a multiple of 4 and >= heads*dh");
     TMF_REQUIRE_ALIGNED(dq); TMF_REQUIRE_ALIGNED(dk); TMF_REQUIRE_ALIGNED(dv);
+    TMF_REQUIRE_ALIGNED(q); TMF_REQUIRE_ALIGNED(k); TMF_REQUIRE_ALIGNED(v); TMF_REQUIRE_ALIGNED(out); TMF_REQUIRE_ALIGNED(dout);
     return xattn_bwd_launch("tmf_xattn_bwd", q, k, v, k, v, out, lse, dout, dq, dk, dv, dk, dv, B, heads, N, M, M, dh,
                             q_stride, kv_stride, dkv_stride, scale, stream);
 }
@@ -583,6 +586,8 @@ extern "C" int tmf_xattn_bwd_cat(const float* q, const float* k1, const float* v
                 "tmf_xattn_bwd_cat: dkv_stride must be a multiple of 4 and >= heads*dh");
     TMF_REQUIRE_ALIGNED(dq); TMF_REQUIRE_ALIGNED(dk1); TMF_REQUIRE_ALIGNED(dv1); TMF_REQUIRE_ALIGNED(dk2);
     TMF_REQUIRE_ALIGNED(dv2);
+    TMF_REQUIRE_ALIGNED(q); TMF_REQUIRE_ALIGNED(k1); TMF_REQUIRE_ALIGNED(v1); TMF_REQUIRE_ALIGNED(k2); TMF_REQUIRE_ALIGNED(v2);
+    TMF_REQUIRE_ALIGNED(out); TMF_REQUIRE_ALIGNED(dout);
     return xattn_bwd_launch("tmf_xattn_bwd_cat", q, k1, v1, k2, v2, out, lse, dout, dq, dk1, dv1, dk2, dv2, B, heads, N,
                             M1 + M2, M1, dh, q_stride, kv_stride, dkv_stride, scale, stream);
 }
