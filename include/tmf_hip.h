@@ -395,6 +395,12 @@ int tmf_xattn_bwd_cat(const float* q, const float* k1, const float* v1, const fl
                       const float* lse, const float* dout, float* dq, float* dk1, float* dv1, float* dk2, float* dv2,
                       int B, int heads, int N, int M1, int M2, int dh, int q_stride, int kv_stride, int dkv_stride,
                       float scale, void* stream);
+/* P = softmax(q k^T scale) rebuilt from the lse that tmf_xattn_fwd / _fwd_cat wrote (base 2).
+ * probs: [B][heads][N][M1+M2] or NULL; recv: [B][heads][M1+M2] = mean over queries of P, or NULL;
+ * at least one non-NULL.  k2 may be NULL when M2 == 0.  dh 8, 16, 32 or 64.  No atomics: two calls give the same bits. */
+int tmf_xattn_probs(const float* q, const float* k1, const float* k2, const float* lse,
+                    float* probs, float* recv, int B, int heads, int N, int M1, int M2, int dh,
+                    int q_stride, int kv_stride, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------
  * LayerNorm over the last dim (networks.py:117,219) and the token pooling of
@@ -725,6 +731,15 @@ size_t tmf_fusion_infer_workspace_bytes(const tmf_fusion_desc* d);
 int    tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
                             const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes,
                             float* cls, void* stream);
+/* The forward-only pass with the attention maps of every Transformer instance (tmf_xattn_probs after each instance's
+ * attention).  Always one launch per op, whatever desc->flags says: cls is bit-identical to tmf_fusion_infer_fwd with
+ * TMF_FUSION_PER_OP.  probs: [2*depth][B][heads][N][N] or NULL; recv: [2*depth][B][heads][N] (required).  Instance 2l =
+ * layer l's mri encoder (queries mri, keys pet), 2l + 1 = its pet encoder (queries pet, keys the NEW mri tokens).
+ * Everything else as tmf_fusion_infer_fwd; workspace >= tmf_fusion_attn_maps_workspace_bytes. */
+size_t tmf_fusion_attn_maps_workspace_bytes(const tmf_fusion_desc* d);
+int    tmf_fusion_attn_maps(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
+                            const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes,
+                            float* cls, float* probs, float* recv, void* stream);
 
 /* ------------------------------------------------------------------------------
  * The dense heads of model_ad in one launch per direction (csrc/heads.hip).  Replaces `self.D(D_MRI_inp)`,

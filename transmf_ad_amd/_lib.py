@@ -106,6 +106,7 @@ PROTOTYPES = {
     "tmf_xattn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "tmf_xattn_fwd_cat": (_i, [_p] * 7 + [_i] * 8 + [_f, _p]),
     "tmf_xattn_bwd_cat": (_i, [_p] * 13 + [_i] * 9 + [_f, _p]),
+    "tmf_xattn_probs": (_i, [_p] * 6 + [_i] * 8 + [_f, _p]),
     "tmf_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     "tmf_pack_conv_weights": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "tmf_pack_conv_weights_bf16": (_i, [_p, _p, _p, _i, _i, _i, _p]),
@@ -197,6 +198,8 @@ PROTOTYPES.update({
                                   C.POINTER(XformerGrads), _p, _p, _p, _z, _p]),
     "tmf_fusion_infer_workspace_bytes": (_z, [C.POINTER(FusionDesc)]),
     "tmf_fusion_infer_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
+    "tmf_fusion_attn_maps_workspace_bytes": (_z, [C.POINTER(FusionDesc)]),
+    "tmf_fusion_attn_maps": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p, _p, _p]),
 })
 
 

@@ -21,6 +21,9 @@
 // torch.cat([mri, pet], 1).  The kernels read key / value row j of batch b from the first part when j < M1, else row
 // j - M1 of the second part, and write dK / dV back the same way, so the concatenated context is never built.
 //
+// Attention maps (tmf_xattn_probs): the probabilities themselves, or their mean over the queries per key, rebuilt on request
+// from q, k and the forward's lse by a kernel of the dK/dV geometry - the only place the (B,h,N,M) tensor is ever written.
+//
 // Replaces, at /root/reference/models/networks.py:166-174: the three rearranges, einsum
 // 'bhid,bhjd->bhij' * scale, Softmax(dim=-1), einsum 'bhij,bhjd->bhid' and their backward.
 #include "tmf_device.h"
@@ -447,6 +450,81 @@ __global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_bwd_dkv_kernel(
     }
 }
 
+// Attention probabilities P = exp2(s scale log2e - lse) rebuilt from the forward's lse, and "attention received"
+// recv[key] = (1/N) sum_query P: the geometry of the dK/dV kernel (a wave owns 32 keys, all queries resident in LDS with
+// their lse, the two waves of a key tile take alternate query tiles).  After the MFMA a lane holds 16 queries of ONE key:
+// the 32 lanes of a lane half write 32 consecutive floats of a probs row, and the column sum is an in-lane loop, one
+// lane <-> lane+32 exchange and a fixed-order merge of the two query halves through LDS - no atomics.
+// probs: [B][heads][N][M] or NULL; recv: [B][heads][M] or NULL.
+template <int DH>
+__global__ __launch_bounds__(256, DH <= 32 ? 2 : 1) void xattn_probs_kernel(
+    const float* __restrict__ q, const float* k, const float* k2, const float* __restrict__ lse, float* __restrict__ probs,
+    float* __restrict__ recv, int heads, int N, int M, int M1, int q_stride, int kv_stride, float scale, int sb) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Qs = smem;
+    float* lses = smem + (sb + 1) * (DH + 1);
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hsel = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int ksp = wave & 1;                                // which half of the query tiles this wave takes
+    const int k0 = (blockIdx.x * 2 + (wave >> 1)) * 32;
+    const int ki = k0 + l31;
+    const float* qb = q + (size_t)b * N * q_stride;
+    const bool part1 = ki < M1;                              // this lane's key row lies in the first context part
+    const size_t krow = part1 ? (size_t)b * M1 + ki : (size_t)b * (M - M1) + (ki - M1);
+    const float* kr = (part1 ? k : k2) + krow * kv_stride;
+    const size_t bh = (size_t)b * heads + h;
+    const float c2 = scale * LOG2E;
+
+    float kreg[DH / 2];
+#pragma unroll
+    for (int s = 0; s < DH / 2; ++s) kreg[s] = ki < M ? kr[h * DH + 2 * s + hsel] : 0.f;
+    float colsum = 0.f;                                      // carried across the super-blocks of the queries
+
+    for (int sb0 = 0; sb0 < N; sb0 += sb) {
+        const int nrows = (N - sb0) < sb ? (N - sb0) : sb;
+        const int nrows_pad = (nrows + 31) & ~31;
+        if (sb0 > 0) __syncthreads();
+        stage_rows<DH>(Qs, qb, qb, N, q_stride, h * DH, sb0, nrows_pad, N, tid, 256);
+        // q * (scale log2e) as the forward forms it ahead of its MFMAs (qreg), so that s below is the forward's score bit for
+        // bit and exp2f(s - lse) the probability its own lse stands for.  A thread scales the float4 units it staged itself
+        // (stage_rows deals unit e to thread e % 256): no barrier in between
+        for (int e = tid; e < nrows_pad * (DH / 4); e += 256) {
+            float* d = Qs + (e / (DH / 4)) * (DH + 1) + (e % (DH / 4)) * 4;
+            d[0] *= c2; d[1] *= c2; d[2] *= c2; d[3] *= c2;
+        }
+        for (int r = tid; r < nrows_pad; r += 256) lses[r] = sb0 + r < N ? lse[bh * N + sb0 + r] : 0.f;
+        __syncthreads();
+        if (k0 < M) {
+            for (int qt = ksp; qt < nrows_pad / 32; qt += 2) {
+                f32x16 s;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] = 0.f;
+                mma_rows<DH>(s, Qs, qt * 32, kreg, l31, hsel);      // s[query][key], in base-2 units
+                // a zero-filled query row has s = 0 and lse 0: p = 1; a zero-filled key has s = 0: exp2f(0 - lse) overflows
+                // for a row whose scores all lie far below zero.  Neither is part of P: nothing summed, nothing written
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qr = qt * 32 + frag_row(r, hsel);
+                    const int qi = sb0 + qr;
+                    const bool live = qi < N && ki < M;
+                    const float p = live ? exp2f(s[r] - lses[qr]) : 0.f;
+                    colsum += p;
+                    if (probs != nullptr && live) probs[(bh * N + qi) * M + ki] = p;
+                }
+            }
+        }
+    }
+    if (recv == nullptr) return;
+    colsum += __shfl_xor(colsum, 32);
+    // sum the two query halves of a key tile through LDS (the panel is dead by now), this half first
+    __syncthreads();
+    float* xch = smem + (wave >> 1) * 32 + l31;
+    if (ksp == 1 && hsel == 0) *xch = colsum;
+    __syncthreads();
+    if (ksp == 0 && hsel == 0 && ki < M) recv[bh * M + ki] = (colsum + *xch) / (float)N;
+}
+
 // rows of the LDS-resident side per super-block: everything if it fits in ~135 KiB, else 512 (256 for dh = 64)
 int resident_rows(int n, int dh) {
     const int cap = dh == 64 ? 256 : 512;
@@ -462,6 +540,8 @@ size_t lds_dkv(int sb, int dh) {
     const size_t panels = (size_t)(2 * (sb + 1) * (dh + 1) + 2 * sb + 64) * 4, merge = (size_t)2 * 64 * (32 * ((dh + 31) / 32)) * 4;
     return panels > merge ? panels : merge;
 }
+// the Q panel, the lse of its rows (the merge area of the column sums, 64 floats, lies inside the panel)
+size_t lds_probs(int sb, int dh) { return (size_t)((sb + 1) * (dh + 1) + sb + 64) * 4; }
 
 int check_attn(const char* fn, int B, int heads, int N, int M, int dh, int q_stride, int kv_stride) {
     TMF_REQUIRE(B > 0 && heads > 0 && N > 0 && M > 0, TMF_E_SHAPE, "%s: non-positive dimension", fn);
@@ -529,7 +609,45 @@ int xattn_bwd_launch(const char* fn, const float* q, const float* k, const float
     return tmf_launch_result("tmf_xattn_bwd(dkv)");
 }
 
+int xattn_probs_launch(const char* fn, const float* q, const float* k, const float* k2, const float* lse, float* probs,
+                       float* recv, int B, int heads, int N, int M, int M1, int dh, int q_stride, int kv_stride, float scale,
+                       void* stream) {
+    TMF_REQUIRE((heads * dh) % 4 == 0, TMF_E_SHAPE, "%s: heads*dh must be a multiple of 4", fn);
+    const int sb = resident_rows(N, dh);
+    const size_t lds = lds_probs(sb, dh);
+    dim3 grid(tmf_cdiv(M, 64), heads, B), block(256);
+    int rc = TMF_OK;
+#define CALL(DH)                                                                                     \
+    auto kf = xattn_probs_kernel<DH>;                                                                \
+    if ((rc = tmf_allow_lds(kf, lds, fn))) return rc;                                                \
+    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)stream, q, k, k2, lse, probs, recv, heads, N, M, M1, q_stride, \
+                       kv_stride, scale, sb);
+    TMF_DH_SWITCH(dh, CALL)
+#undef CALL
+    return tmf_launch_result(fn);
+}
+
 }  // namespace
+
+extern "C" int tmf_xattn_probs(const float* q, const float* k1, const float* k2, const float* lse, float* probs, float* recv,
+                               int B, int heads, int N, int M1, int M2, int dh, int q_stride, int kv_stride, float scale,
+                               void* stream) {
+    TMF_REQUIRE_PTR(q); TMF_REQUIRE_PTR(k1); TMF_REQUIRE_PTR(lse);
+    TMF_REQUIRE(probs != nullptr || recv != nullptr, TMF_E_NULL, "tmf_xattn_probs: arguments 'probs' and 'recv' are both NULL");
+    TMF_REQUIRE(M2 >= 0, TMF_E_SHAPE, "tmf_xattn_probs: M2 = %d", M2);
+    if (M2 > 0) {
+        TMF_REQUIRE_PTR(k2);
+        int rc = check_parts("tmf_xattn_probs", M1, M2);
+        if (rc) return rc;
+    } else {
+        k2 = k1;
+    }
+    int rc = check_attn("tmf_xattn_probs", B, heads, N, M1 + M2, dh, q_stride, kv_stride);
+    if (rc) return rc;
+    TMF_REQUIRE_ALIGNED(q); TMF_REQUIRE_ALIGNED(k1); TMF_REQUIRE_ALIGNED(k2);
+    return xattn_probs_launch("tmf_xattn_probs", q, k1, k2, lse, probs, recv, B, heads, N, M1 + M2, M1, dh, q_stride,
+                              kv_stride, scale, stream);
+}
 
 extern "C" int tmf_xattn_fwd(const float* q, const float* k, const float* v, float* out, float* lse,
                              int B, int heads, int N, int M, int dh, int q_stride, int kv_stride, float scale,

@@ -378,6 +378,47 @@ extern "C" int tmf_fusion_infer_fwd(const tmf_fusion_desc* d, const float* mri_t
     return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + ip.arg), d->B, d->N, d->dim, stream);
 }
 
+// The forward-only pass with every instance's attention maps.  Always one launch per op (dim 128 too): the fused kernels of
+// xformer_fused.hip keep P in registers and their q / k live in fragment-order panels, while instance_fwd leaves q, k | v and
+// lse of the instance in the reused slab, where tmf_xattn_probs reads them before the next instance overwrites them.
+static tmf_fusion_desc per_op_desc(const tmf_fusion_desc* d) {
+    tmf_fusion_desc e = *d;
+    e.flags |= TMF_FUSION_PER_OP;
+    return e;
+}
+
+extern "C" size_t tmf_fusion_attn_maps_workspace_bytes(const tmf_fusion_desc* d) {
+    if (check_desc("tmf_fusion_attn_maps_workspace_bytes", d) != TMF_OK) return 0;
+    return make_infer_plan(per_op_desc(d)).bytes;
+}
+
+extern "C" int tmf_fusion_attn_maps(const tmf_fusion_desc* d, const float* mri_tok, const float* pet_tok,
+                                    const tmf_xformer_params* inst, void* workspace, size_t workspace_bytes, float* cls,
+                                    float* probs, float* recv, void* stream) {
+    TMF_TRY(check_fwd_args(__func__, d, mri_tok, pet_tok, inst, workspace, "workspace", cls));
+    TMF_REQUIRE_PTR(recv);
+    const tmf_fusion_desc e = per_op_desc(d);
+    const InferPlan ip = make_infer_plan(e);
+    const Plan& p = ip.p;
+    TMF_REQUIRE(workspace_bytes >= ip.bytes, TMF_E_WORKSPACE, "tmf_fusion_attn_maps: workspace %zu B < required %zu B",
+                workspace_bytes, ip.bytes);
+    TMF_TRY(check_params("tmf_fusion_attn_maps", inst, 2 * e.depth));
+    char* base = (char*)workspace;
+    char* sv = base + ip.slab;
+    const float* m = mri_tok;
+    const float* q = pet_tok;
+    const float scale = 1.0f / sqrtf((float)e.dim_head);
+    const size_t per_recv = (size_t)e.B * e.heads * e.N, per_probs = per_recv * e.N;
+    for (int i = 0; i < 2 * e.depth; ++i) {
+        float* y = F(base, ip.tok[i & 1][(i >> 1) & 1]);
+        TMF_TRY(instance_fwd(e, p, inst[i], (i & 1) ? q : m, (i & 1) ? m : q, sv, stream, y));
+        TMF_TRY(tmf_xattn_probs(F(sv, p.I.q), F(sv, p.I.kv), nullptr, F(sv, p.I.lse), probs ? probs + i * per_probs : nullptr,
+                                recv + i * per_recv, e.B, e.heads, e.N, e.N, 0, e.dim_head, p.inner, 2 * p.inner, scale, stream));
+        if (i & 1) q = y; else m = y;
+    }
+    return tmf_token_pool_fwd(m, q, cls, (int32_t*)(base + ip.arg), e.B, e.N, e.dim, stream);
+}
+
 // Backward of one instance.  dy = gradient w.r.t. its output y.  Writes
 //   dx_out   = dy + d(LN_f path)/dx                       (gradient w.r.t. the instance's own input tokens)
 //   dctx_out = dctx_acc + d/d(context tokens)             (dctx_acc: what the context tensor has collected so far)

@@ -333,24 +333,29 @@ class CrossTransformer_MOD_AVG(nn.Module):
                     return False
         return True
 
+    def _one_call_args(self):
+        """(cfg, params) as the one-call entries of ops take them (FusionTrain, fusion_infer, fusion_attn_maps)."""
+        params, eps, drops = [], [], []
+        for pair in self.layers:
+            for tr in pair:
+                pa, pf = tr.layers[0]
+                a, f = pa.fn, pf.fn
+                drops.append((a.to_out[1], f.net[2], f.net[4]))
+                params += [pa.norm.weight, pa.norm.bias, a.to_q.weight, a.to_kv.weight, a.to_out[0].weight,
+                           a.to_out[0].bias, pf.norm.weight, pf.norm.bias, f.net[0].weight, f.net[0].bias,
+                           f.net[3].weight, f.net[3].bias, tr.norm.weight, tr.norm.bias]
+                eps.append((float(pa.norm.eps), float(pf.norm.eps), float(tr.norm.eps)))
+        a0 = self.layers[0][0].layers[0][0].fn
+        f0 = self.layers[0][0].layers[0][1].fn
+        cfg = (a0.heads, a0.to_q.out_features // a0.heads, f0.net[0].out_features, len(self.layers), tuple(eps),
+               tuple(drops) if any(tr._dropout_active() for pair in self.layers for tr in pair) else None)
+        return cfg, params
+
     @device_guard
     def forward(self, mri_tokens, pet_tokens):
         train_call = self._one_call_ok(mri_tokens)
         if train_call or (pet_tokens.shape == mri_tokens.shape and self._infer_one_call_ok(mri_tokens)):
-            params, eps, drops = [], [], []
-            for pair in self.layers:
-                for tr in pair:
-                    pa, pf = tr.layers[0]
-                    a, f = pa.fn, pf.fn
-                    drops.append((a.to_out[1], f.net[2], f.net[4]))
-                    params += [pa.norm.weight, pa.norm.bias, a.to_q.weight, a.to_kv.weight, a.to_out[0].weight,
-                               a.to_out[0].bias, pf.norm.weight, pf.norm.bias, f.net[0].weight, f.net[0].bias,
-                               f.net[3].weight, f.net[3].bias, tr.norm.weight, tr.norm.bias]
-                    eps.append((float(pa.norm.eps), float(pf.norm.eps), float(tr.norm.eps)))
-            a0 = self.layers[0][0].layers[0][0].fn
-            f0 = self.layers[0][0].layers[0][1].fn
-            cfg = (a0.heads, a0.to_q.out_features // a0.heads, f0.net[0].out_features, len(self.layers), tuple(eps),
-                   tuple(drops) if any(tr._dropout_active() for pair in self.layers for tr in pair) else None)
+            cfg, params = self._one_call_args()
             if not train_call:
                 return ops.fusion_infer(mri_tokens, pet_tokens, cfg, params)
             return ops.FusionTrain.apply(mri_tokens, pet_tokens, cfg, *params)

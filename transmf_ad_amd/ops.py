@@ -1256,6 +1256,48 @@ def fusion_infer(mri_tok, pet_tok, cfg, params):
     return cls
 
 
+def xattn_probs(q, kv, lse, heads, scale, kv2=None, want_probs=True):
+    """The attention probabilities of cross_attention(q, kv, ...) rebuilt from its base-2 log-sum-exp `lse` (B, heads, N)
+    (tmf_xattn_probs, csrc/attention.hip): q (B, N, h*d), kv (B, M1, 2*h*d), kv2 (B, M2, 2*h*d) or None, the second part of a
+    two-part context -> (probs (B, heads, N, M1 + M2) or None, recv (B, heads, M1 + M2) = the mean of probs over the queries)."""
+    q, kv, lse = _chk(q, "q"), _chk(kv, "kv"), _chk(lse, "lse")
+    B, N, inner = q.shape
+    M1 = kv.shape[1]
+    if kv.shape[0] != B or kv.shape[2] != 2 * inner or inner % heads or tuple(lse.shape) != (B, heads, N):
+        raise _lib.TmfError(f"attention shapes: q {tuple(q.shape)} kv {tuple(kv.shape)} lse {tuple(lse.shape)} heads {heads}")
+    M2 = 0
+    if kv2 is not None:
+        kv2 = _chk(kv2, "kv2")
+        M2 = kv2.shape[1]
+        if kv2.shape[0] != B or kv2.shape[2] != 2 * inner or M2 == 0:
+            raise _lib.TmfError(f"attention shapes: kv2 {tuple(kv2.shape)} against kv {tuple(kv.shape)}")
+    probs = torch.empty((B, heads, N, M1 + M2), device=q.device, dtype=_f32) if want_probs else None
+    recv = torch.empty((B, heads, M1 + M2), device=q.device, dtype=_f32)
+    _lib.call("tmf_xattn_probs", q.data_ptr(), kv.data_ptr(), _ptr(kv2), lse.data_ptr(), _ptr(probs), recv.data_ptr(),
+              B, heads, N, M1, M2, inner // heads, inner, 2 * inner, float(scale), _stream())
+    return probs, recv
+
+
+def fusion_attn_maps(mri_tok, pet_tok, cfg, params, want_probs):
+    """fusion_infer with the attention maps of every Transformer instance (tmf_fusion_attn_maps, csrc/fusion_path.hip; always
+    one launch per op): -> (cls (B, 4*dim), recv (2*depth, B, heads, N), probs (2*depth, B, heads, N, N) or None).  Instance
+    2l: layer l's mri encoder (queries mri, keys pet); 2l + 1: its pet encoder (queries pet, keys the new mri tokens)."""
+    import ctypes as C
+    mri, pet, desc, inst, masks = _fusion_call_setup(mri_tok, pet_tok, cfg, params)
+    nws = _lib.query("tmf_fusion_attn_maps_workspace_bytes", C.byref(desc))
+    if nws == 0:
+        raise _lib.TmfError("tmf_fusion_attn_maps_workspace_bytes: " + (_lib.load().tmf_last_error_string() or b"").decode())
+    B, N, dim = mri.shape
+    n_inst = 2 * desc.depth
+    ws = torch.empty(nws, device=mri.device, dtype=torch.uint8)
+    cls = torch.empty((B, 4 * dim), device=mri.device, dtype=_f32)
+    recv = torch.empty((n_inst, B, desc.heads, N), device=mri.device, dtype=_f32)
+    probs = torch.empty((n_inst, B, desc.heads, N, N), device=mri.device, dtype=_f32) if want_probs else None
+    _lib.call("tmf_fusion_attn_maps", C.byref(desc), mri.data_ptr(), pet.data_ptr(), inst, ws.data_ptr(), nws,
+              cls.data_ptr(), _ptr(probs), recv.data_ptr(), _stream())
+    return cls, recv, probs
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
