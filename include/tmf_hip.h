@@ -21,6 +21,14 @@
  *  - Return: 0 = launched; <0 = TMF_E_* argument error (nothing launched);
  *    >0 = hipError_t from the launch.  tmf_last_error_string() describes the last
  *    non-zero return on the calling thread.
+ *
+ * How this file is written (transmf_ad_amd/_lib.py parses it at import into the ctypes prototypes, Structure classes and
+ * constants, and refuses what it cannot map):
+ *  - one declaration per `;`, every parameter named, no function pointers;
+ *  - scalar types int, long, long long, unsigned long long, size_t, float, double (struct fields also int32_t);
+ *  - structs as `typedef struct tmf_x { ... } tmf_x;`, array sizes literal or a TMF_* define;
+ *  - a `tmf_x*` parameter is a HOST struct, except tmf_augment_decision (records in device memory);
+ *  - constants as `#define TMF_NAME <integer>`; function-like macros are not exported.
  */
 #ifndef TMF_HIP_H
 #define TMF_HIP_H
@@ -621,6 +629,21 @@ int    tmf_batch_augment(const float* store_mri, const float* store_pet, const i
 #define TMF_SNET_ALGO_POOL_REC_BN 0x20000
 int  tmf_snet_algo_flags(void);
 int  tmf_c1_split_mode(void);                     /* the option "c1_split" (tmf_set_option) */
+/* The kernel family of one encoder block (Conv3d(cin -> cout, ksize) ahead of BatchNorm) per direction, under the options of the
+ * moment ("conv_wino"; inside a call with TMF_SNET_ALGO that call's word): forward in bits 0-3, data gradient in bits 4-7,
+ * weight gradient in bits 8-11, each a TMF_CONV_* code.  The ONE rule: the whole-encoder entries plan with it and the Python
+ * binding's block-by-block path asks it, so the two run the same kernels.
+ *   TMF_PREC_BF16,  ksize 3, cin > 1, cin % 8 == 0: forward and weight gradient BF16; data gradient BF16 when cout % 8 == 0;
+ *   TMF_PREC_FP32X, the same condition:             forward SPLIT; data gradient SPLIT when cout % 8 == 0; weight gradient direct;
+ *   TMF_PREC_FP32,  ksize 3, cin > 1:               forward WINO at conv_wino >= 2 with tmf_conv3d_wino_ok(cin, cout), data gradient
+ *                                                   WINO at >= 1 with tmf_conv3d_wino_ok(cout, cin), weight gradient WINO at >= 3
+ *                                                   with tmf_conv3d_wgrad_wino_ok(cin, cout);
+ * everything else TMF_CONV_DIRECT (the first block, cin == 1, has its fused passes: tmf_c1_*).  -1: unknown precision. */
+#define TMF_CONV_DIRECT 0         /* exact fp32 MFMA, direct form (tmf_conv3d_fwd / tmf_conv3d_wgrad) */
+#define TMF_CONV_WINO   1         /* Winograd form (tmf_conv3d_fwd_wino / tmf_conv3d_wgrad_wino) */
+#define TMF_CONV_BF16   2         /* operands rounded to bf16 (tmf_conv3d_fwd_bf16_t / tmf_conv3d_wgrad_bf16_t) */
+#define TMF_CONV_SPLIT  3         /* exact 3-way bf16 split (tmf_conv3d_fwd_split) */
+int  tmf_conv_block_algo(int precision, int cin, int cout, int ksize);
 typedef struct tmf_snet_desc {
     int   B, D, H, W;                /* input volumes (B, 1, D, H, W) */
     int   dim;                       /* sNet(dim) */
@@ -893,6 +916,7 @@ int    tmf_adv_criterion_bwd(const float* g_logits, const float* g_mri, const fl
  * (int64); [2] sum of losses[0], [3] sum of losses[1] (double); [4], [5], [6] samples whose argmax (the first maximal
  * index; a NaN counts as the maximum, as in torch.argmax) equals the target, for logits / label, d_mri / 1, d_pet / 0
  * (int64); [7] unused.  losses: the two device floats of tmf_adv_criterion_fwd. */
+#define TMF_TRAIN_METRICS_WORDS 8
 int    tmf_train_metrics_update(void* state, const float* losses, const float* logits, const float* d_mri, const float* d_pet,
                                 const long long* label, int B, int C, void* stream);
 /* The evaluator's metrics of :183-187 (ignite Accuracy, ConfusionMatrix, ROC_AUC, Loss): one launch, one workgroup.

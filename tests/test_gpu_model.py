@@ -688,19 +688,31 @@ def test_train_step_is_bit_reproducible_with_two_streams(mode):
         T.set_activation_storage("fp32")
 
 
-@pytest.mark.parametrize("mode", ["fp32", "bf16", "bf16s", "fp32x"])
-@pytest.mark.parametrize("name", ["ad_ragged", "ad_mid"])
+def _set_conv_wino(value):
+    from transmf_ad_amd import _lib
+    _lib.call("tmf_set_option", b"conv_wino", value)
+
+
+# "-winoN": the process option conv_wino at N (default 3).  ad_ragged (dim 32, 35x38x33, batch 3) is the smallest fixture at
+# which the families are mixed per block and direction: block 16 -> 32 runs its forward in the Winograd form and its data
+# gradient direct, block 32 -> 64 all three in it, the narrower blocks nothing; the ragged volume takes padded bricks.
+@pytest.mark.parametrize("name, mode", [(n, m) for m in ("fp32", "bf16", "bf16s", "fp32x") for n in ("ad_ragged", "ad_mid")]
+                         + [("ad_ragged", f"fp32-wino{w}") for w in (0, 1, 2)])
 def test_one_call_encoder_is_bit_identical_to_block_by_block(name, mode):
     """tmf_snet_train_fwd / _bwd (one library call per encoder pass, csrc/snet_path.hip) enqueue exactly the launches of
     the block-by-block path: logits, loss, every gradient and every BatchNorm buffer are bit-identical (fp32x since round 4:
-    TMF_PREC_FP32X, weights split by tmf_pack_conv_weights_split3)."""
+    TMF_PREC_FP32X, weights split by tmf_pack_conv_weights_split3).  Both paths take each block's kernel family from
+    tmf_conv_block_algo; the -winoN cases run them at the other settings of conv_wino."""
     import transmf_ad_amd as T
     from transmf_ad_amd import ops
     g = Golden(name)
+    mode, _, wino = mode.partition("-wino")
     T.set_conv_precision(mode if mode in ("fp32", "fp32x") else "bf16")
     T.set_activation_storage("bf16" if mode == "bf16s" else "fp32")
     res = []
     try:
+        if wino:
+            _set_conv_wino(int(wino))
         for one_call in (True, False):
             ops.SNET_ONE_CALL = one_call
             net = build(g)
@@ -710,6 +722,7 @@ def test_one_call_encoder_is_bit_identical_to_block_by_block(name, mode):
             res.append((outs, loss, {k: p.grad.clone() for k, p in net.named_parameters()},
                         {k: b.clone() for k, b in net.named_buffers()}))
     finally:
+        _set_conv_wino(3)
         ops.SNET_ONE_CALL = True
         T.set_activation_storage("fp32")
         T.set_conv_precision("fp32")
@@ -733,21 +746,25 @@ def test_one_call_encoder_is_taken_by_default():
     assert type(out.grad_fn.next_functions[0][0]).__name__.startswith("SNetTrain"), out.grad_fn.next_functions
 
 
-@pytest.mark.parametrize("mode", ["fp32", "bf16", "bf16s"])
-@pytest.mark.parametrize("name", ["ad_tiny", "ad_adni_b2"])
+@pytest.mark.parametrize("name, mode", [(n, m) for m in ("fp32", "bf16", "bf16s") for n in ("ad_tiny", "ad_adni_b2")]
+                         + [("ad_tiny", "fp32-wino0")])
 def test_one_call_eval_encoder_is_bit_identical_to_block_by_block(name, mode):
     """tmf_snet_eval_fwd (val_step's encoder as one library call; the bf16 modes since round 4) enqueues the launches of the
     block-by-block eval path: after one train step (so the running statistics are not the initial ones) the eval tokens of
-    both are bit-identical, and the one-call path really is the one taken."""
+    both are bit-identical, and the one-call path really is the one taken.  fp32-wino0: conv_wino 0, no block in the
+    Winograd form of the one-kernel block."""
     import transmf_ad_amd as T
     from transmf_ad_amd import ops
     g = Golden(name)
+    mode, _, wino = mode.partition("-wino")
     T.set_conv_precision("fp32" if mode == "fp32" else "bf16")
     T.set_activation_storage("bf16" if mode == "bf16s" else "fp32")
     toks = []
     calls = []
     orig = ops.snet_eval_one_call
     try:
+        if wino:
+            _set_conv_wino(int(wino))
         net = build(g)
         step(net, g, train=True)
         net.eval()
@@ -758,6 +775,7 @@ def test_one_call_eval_encoder_is_bit_identical_to_block_by_block(name, mode):
             with torch.no_grad():
                 toks.append((net.mri_cnn.forward_channels_last(mri), net.pet_cnn.forward_channels_last(pet)))
     finally:
+        _set_conv_wino(3)
         ops.snet_eval_one_call = orig
         ops.SNET_ONE_CALL = True
         T.set_activation_storage("fp32")

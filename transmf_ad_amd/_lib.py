@@ -1,4 +1,11 @@
-"""ctypes binding of libtmf_hip.so (C ABI: include/tmf_hip.h).
+"""ctypes binding of libtmf_hip.so, DERIVED from its C ABI header include/tmf_hip.h.
+
+parse_header() reads the header at import and yields everything the binding needs, so nothing is kept in step by hand:
+  PROTOTYPES   name -> (restype, argtypes) of every declared function;
+  the Structure classes (tmf_snet_desc -> SnetDesc, tmf_xformer_params -> XformerParams, ...);
+  the integer #defines without their TMF_ prefix (POOL_MAX2, SNET_ALONE, ADAM_MAX_TENSORS, ...; all of them in CONSTANTS).
+The header states the conventions the parser relies on.  It fails closed: a declaration, parameter type, struct field or
+#define it cannot map raises HeaderError with the line, it never guesses.
 
 There is NO fallback: if the library is missing, or a call returns non-zero, this
 module raises.  The product path never routes around the HIP kernels.
@@ -7,281 +14,133 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+
+from .build import ABI_HEADER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtmf_hip.so")
 
-POOL_NONE, POOL_MAX2, POOL_AVG2 = 0, 1, 2
-DW_TAPMAJOR, DW_REFERENCE = 0, 1
-_POOL = {None: POOL_NONE, "none": POOL_NONE, "max": POOL_MAX2, "avg": POOL_AVG2}
-
-_p = C.c_void_p
-_i = C.c_int
-_f = C.c_float
-_l = C.c_long
-_d = C.c_double
-_z = C.c_size_t
-
-# name -> (restype, argtypes); mirrors include/tmf_hip.h declaration by declaration
-PROTOTYPES = {
-    "tmf_version": (_i, []),
-    "tmf_last_error_string": (C.c_char_p, []),
-    "tmf_set_option": (_i, [C.c_char_p, _i]),
-    "tmf_conv3d_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_fwd_affine": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_conv3d_stat_blocks": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_fwd_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_fwd_bf16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_wgrad_bf16_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_bf16": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_fwd_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_bf16_stat_blocks": (_i, [_i, _i, _i, _i]),
-    "tmf_conv3d_split_stat_blocks": (_i, [_i, _i, _i, _i]),
-    "tmf_conv3d_fwd_wino": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_wino_ok": (_i, [_i, _i]),
-    "tmf_conv3d_fwd_wino_affine": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_conv3d_wino_stat_blocks": (_i, [_i, _i, _i, _i]),
-    "tmf_conv3d_wino_bricks": (_i, [_i, _i, _i, _i]),
-    "tmf_conv3d_wino_bricks2": (_i, [_i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wino_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_wino_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wino_kernel_name2": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_wino_tiles": (C.c_long, [_i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wino_weight_bytes": (_z, [_i, _i]),
-    "tmf_wino_x_mode": (_i, []),
-    "tmf_c1_split_mode": (_i, []),
-    "tmf_snet_algo_flags": (_i, []),
-    "tmf_conv_wino_mode": (_i, []),
-    "tmf_wino_p_mode": (_i, []),
-    "tmf_conv3d_wgrad_wino_ok": (_i, [_i, _i]),
-    "tmf_conv3d_wgrad_wino_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_wino": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_fwd_bf16_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_wgrad_bf16_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
-    "tmf_conv3d_c1_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_c1_stat_blocks": (_i, [_i, _i, _i, _i, _i]),
-    "tmf_conv3d_c1_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_conv3d_c1_wgrad": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_c1_blocks": (_i, [_i, _i, _i, _i, _i]),
-    "tmf_c1_stats": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "tmf_c1_gram_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_c1_gram_bytes_bf16": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_c1_stats_g": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
-    "tmf_c1_bwd_fused_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_c1_bwd_fused": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_stats_g_bf16": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
-    "tmf_c1_bwd_fused_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
-    "tmf_c1_bn_pool_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_c1_bn_pool_fwd_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_c1_bwd_fused_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_c1_stats_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "tmf_c1_bn_pool_fwd_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_reduce_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_wgrad_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
-    "tmf_conv3d_fwd_bf16_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_conv3d_wgrad_bf16_t": (_i, [_p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "tmf_bn_act_pool_fwd_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_bn_act_pool_bwd_reduce_t": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_bn_act_pool_fwd_route": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_bn_act_pool_bwd_reduce_route": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_bn_act_pool_bwd_apply_t": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_c1_bwd_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_fused_coef": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "tmf_c1_bwd_dgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "tmf_c1_bwd_dgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_bn_finalize": (_i, [_p, _i, _i, _d, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p]),
-    "tmf_bn_eval_coeffs": (_i, [_p, _p, _p, _p, _p, _f, _i, _p, _p, _p]),
-    "tmf_bn_act_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_bn_act_pool_bwd_blocks": (_i, [_i, _i, _i, _i, _i, _i]),
-    "tmf_bn_act_pool_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_bn_bwd_finalize": (_i, [_p, _i, _i, _d, _p, _p, _p, _p]),
-    "tmf_bn_act_pool_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_colsum_finalize": (_i, [_p, _i, _i, _p, _p]),
-    "tmf_xattn_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_xattn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "tmf_xattn_fwd_cat": (_i, [_p] * 7 + [_i] * 8 + [_f, _p]),
-    "tmf_xattn_bwd_cat": (_i, [_p] * 13 + [_i] * 9 + [_f, _p]),
-    "tmf_xattn_probs": (_i, [_p] * 6 + [_i] * 8 + [_f, _p]),
-    "tmf_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
-    "tmf_pack_conv_weights": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "tmf_pack_conv_weights_bf16": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "tmf_pack_conv_weights_split3": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "tmf_pack_conv_weights_wino": (_i, [_p, _p, _p, _i, _i, _p]),
-    "tmf_pack_conv_weights_wino_multi": (_i, [_i, _p, _p, _p, _p, _p, _p]),
-    "tmf_layout_ncdhw_to_ndhwc": (_i, [_p, _p, _i, _i, _l, _p]),
-    "tmf_layout_ndhwc_to_ncdhw": (_i, [_p, _p, _i, _i, _l, _p]),
-    "tmf_tok_row_blocks": (_i, [_i]),
-    "tmf_tok_wgrad_multi_workspace_bytes": (_z, [_i, _p, _p]),
-    "tmf_tok_wgrad_multi": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "tmf_tok_linear_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p]),
-    "tmf_tok_linear_bwd_input": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
-    "tmf_layernorm_bwd_blocks": (_i, [_i, _i]),
-    "tmf_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "tmf_tok_linear_fwd_masked": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
-    "tmf_tok_linear_bwd_input_masked": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
-    "tmf_layernorm_bwd_masked": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
-    "tmf_mask_mul": (_i, [_p, _p, _p, _l, _p]),
-    "tmf_token_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "tmf_token_pool_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-}
+_SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_FIELD_SCALARS = dict(_SCALARS, int32_t=C.c_int32)
+_POINTEES = set(_FIELD_SCALARS) | {"void", "char", "unsigned char", "int64_t"}      # what a plain (void*) pointer may point to
+_DEVICE_STRUCTS = {"tmf_augment_decision"}      # records in device memory: a pointer to one is a device pointer
+_TYPE_WORDS = {"const", "unsigned", "void", "char"} | set(_FIELD_SCALARS) | _POINTEES
 
 
-
-class SnetDesc(C.Structure):
-    """tmf_snet_desc (include/tmf_hip.h)"""
-    _fields_ = [("B", _i), ("D", _i), ("H", _i), ("W", _i), ("dim", _i), ("precision", _i), ("storage_bf16", _i),
-                ("momentum", _f * 7), ("eps", _f * 7), ("slope", _f * 7), ("flags", _i)]
-SNET_ALONE = 1
+class HeaderError(ValueError):
+    pass
 
 
-class SnetParams(C.Structure):
-    _fields_ = [("weight", _p * 7), ("bias", _p * 7), ("gamma", _p * 7), ("beta", _p * 7),
-                ("running_mean", _p * 7), ("running_var", _p * 7)]
+def parse_header(text: str):
+    """-> (constants: TMF_NAME -> int, structs: C name -> Structure class, prototypes: name -> (restype, argtypes))."""
+    blank = lambda m: re.sub(r"[^\n]", " ", m.group())          # erase, keeping every line where it was
+    text = re.sub(r"/\*.*?\*/", blank, text, flags=re.S)
+
+    def fail(pos, what):
+        raise HeaderError(f"include/tmf_hip.h:{text.count(chr(10), 0, pos) + 1}: {what}")
+
+    constants = {}
+    for m in re.finditer(r"^#define[ \t]+(\w+)(\(\w*\))?[ \t]*(.*)$", text, flags=re.M):
+        name, macro_args, value = m.group(1), m.group(2), m.group(3).strip()
+        if macro_args or not value:             # function-like macro / include guard
+            continue
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            fail(m.start(), f"#define {name} {value!r} is not an integer")
+    text = re.sub(r"^#ifdef __cplusplus\n.*?\n#endif", blank, text, flags=re.S | re.M)
+    text = re.sub(r"^#.*$", blank, text, flags=re.M)
+
+    structs = {}
+
+    def ctype_of(pos, decl, what, is_return=False):
+        """The ctypes type of `decl` = a C type without its name (parameter or return type)."""
+        base = " ".join(w for w in decl.replace("*", " ").split() if w != "const")
+        stars = decl.count("*")
+        if stars == 0:
+            if base == "void" and is_return:
+                return None
+            if base in _SCALARS:
+                return _SCALARS[base]
+        elif stars == 1 and base == "char":
+            return C.c_char_p
+        elif stars == 1 and base in structs:
+            return C.c_void_p if base in _DEVICE_STRUCTS else C.POINTER(structs[base])
+        elif base in _POINTEES:
+            return C.c_void_p
+        fail(pos, f"{what}: unknown type {decl.strip()!r}")
+
+    def struct_of(m):
+        cname, body = m.group(1), m.group(2)
+        if m.group(3) != cname:
+            fail(m.start(), f"typedef struct {cname} is named {m.group(3)}")
+        fields = []
+        for d in re.finditer(r"[^;]+", body):
+            if not d.group().strip():
+                continue
+            t = re.fullmatch(r"\s*(?:const\s+)?((?:unsigned\s+)?(?:long\s+long|\w+))\s*(.+)", d.group(), flags=re.S)
+            if not t:
+                fail(m.start(2) + d.start(), f"{cname}: cannot read field {d.group().strip()!r}")
+            for item in t.group(2).split(","):
+                f = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", item)
+                base = " ".join(t.group(1).split())
+                if not f or f.group(2) in _TYPE_WORDS or base not in (_POINTEES if f and f.group(1) else _FIELD_SCALARS):
+                    fail(m.start(2) + d.start(), f"{cname}: cannot map field {item.strip()!r} of type {base!r}")
+                ct = C.c_void_p if f.group(1) else _FIELD_SCALARS[base]
+                if f.group(3):
+                    n = int(f.group(3)) if f.group(3).isdigit() else constants.get(f.group(3))
+                    if not isinstance(n, int) or n <= 0:
+                        fail(m.start(2) + d.start(), f"{cname}.{f.group(2)}: unknown array size {f.group(3)!r}")
+                    ct = ct * n
+                fields.append((f.group(2), ct))
+        pyname = "".join(w.capitalize() for w in cname[4:].split("_"))
+        structs[cname] = type(pyname, (C.Structure,), {"_fields_": fields, "__doc__": f"{cname} (include/tmf_hip.h)"})
+        return blank(m)
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", struct_of, text, flags=re.S)
+
+    prototypes = {}
+    for d in re.finditer(r"[^;]+", text):
+        if not d.group().strip():
+            continue
+        pos = d.start() + len(d.group()) - len(d.group().lstrip())
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\b(tmf_\w+)\s*\(([^()]*)\)\s*", d.group())
+        if not m:
+            fail(pos, f"not a function declaration: {' '.join(d.group().split())[:80]!r}")
+        name, args = m.group(2), []
+        for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            a = re.fullmatch(r"\s*(.*\S)\s*\b(\w+)\s*", p, flags=re.S)
+            if not a or a.group(2) in _TYPE_WORDS:
+                fail(pos, f"{name}: unnamed parameter {' '.join(p.split())!r}")
+            args.append(ctype_of(pos, a.group(1), f"{name}, parameter {a.group(2)}"))
+        prototypes[name] = (ctype_of(pos, m.group(1), f"{name}, return", is_return=True), args)
+    return constants, structs, prototypes
 
 
-class SnetGrads(C.Structure):
-    _fields_ = [("dweight", _p * 7), ("dbias", _p * 7), ("dgamma", _p * 7), ("dbeta", _p * 7), ("deep_event", _p)]
-SNET_DEEP_FROM = 3
-MASK_SEGMENTS = 20           # TMF_MASK_SEGMENTS
+with open(ABI_HEADER) as _f:
+    CONSTANTS, STRUCTS, PROTOTYPES = parse_header(_f.read())
+globals().update({k[4:]: v for k, v in CONSTANTS.items()})                  # TMF_POOL_MAX2 -> POOL_MAX2, ...
+globals().update({s.__name__: s for s in STRUCTS.values()})                 # tmf_snet_desc -> SnetDesc, ...
 
 
-PROTOTYPES.update({
-    "tmf_scale_intensity_workspace_bytes": (_z, [_i]),
-    "tmf_volume_minmax": (_i, [_p, _p, _p, _z, _i, _l, _p]),
-    "tmf_scale_flip": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "tmf_rotate_x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "tmf_zoom_area": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "tmf_batch_augment": (_i, [_p] * 7 + [_i] * 5 + [_p]),
-    "tmf_snet_saved_bytes": (_z, [C.POINTER(SnetDesc)]),
-    "tmf_snet_bwd_scratch_bytes": (_z, [C.POINTER(SnetDesc)]),
-    "tmf_snet_train_fwd": (_i, [C.POINTER(SnetDesc), _p, C.POINTER(SnetParams), _p, _z, _p, _p]),
-    "tmf_snet_train_bwd": (_i, [C.POINTER(SnetDesc), _p, _p, _z, _p, C.POINTER(SnetGrads), _p, _z, _p]),
-    "tmf_snet_train_bwd_input": (_i, [C.POINTER(SnetDesc), _p, _p, _z, _p, C.POINTER(SnetGrads), _p, _z, _p, _p]),
-    "tmf_snet_eval_workspace_bytes": (_z, [C.POINTER(SnetDesc)]),
-    "tmf_snet_eval_fwd": (_i, [C.POINTER(SnetDesc), _p, C.POINTER(SnetParams), _p, _z, _p, _p]),
-})
+_c = lambda name: CONSTANTS["TMF_" + name]
+_POOL = {None: _c("POOL_NONE"), "none": _c("POOL_NONE"), "max": _c("POOL_MAX2"), "avg": _c("POOL_AVG2")}
+PRECISION = {"fp32": _c("PREC_FP32"), "bf16": _c("PREC_BF16"), "fp32x": _c("PREC_FP32X")}     # tmf_snet_desc.precision
 
 
-
-class FusionDesc(C.Structure):
-    _fields_ = [(n, _i) for n in ("B", "N", "dim", "heads", "dim_head", "mlp", "depth", "flags")]
-
-
-FUSION_PER_OP = 1
+def snet_algo_wino(m: int) -> int:
+    """TMF_SNET_ALGO_WINO(m): the conv_wino field of a tmf_snet_desc.flags word (a function-like macro, not parsed)."""
+    return (m & 3) << 9
 
 
-XFORMER_PTRS = ("ln1_g", "ln1_b", "wq", "wkv", "wo", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2", "lnf_g", "lnf_b")
-
-
-class XformerParams(C.Structure):
-    _fields_ = ([(n, _p) for n in XFORMER_PTRS] + [("eps1", _f), ("eps2", _f), ("epsf", _f)]
-                + [(n, _p) for n in ("mask_o", "mask_g", "mask_f")])
-
-
-class XformerGrads(C.Structure):
-    _fields_ = [(n, _p) for n in ("small", "lnf", "dwq", "dwkv", "dwo", "dw1", "dw2")]
-
-
-PROTOTYPES.update({
-    "tmf_debug_xf_trace": (None, [_p, _p, _p]),
-    "tmf_fusion_saved_bytes": (_z, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_uses_fused": (_i, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_takes_masks": (_i, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_bwd_scratch_bytes": (_z, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_train_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
-    "tmf_fusion_train_bwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p,
-                                  C.POINTER(XformerGrads), _p, _p, _p, _z, _p]),
-    "tmf_fusion_infer_workspace_bytes": (_z, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_infer_fwd": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p]),
-    "tmf_fusion_attn_maps_workspace_bytes": (_z, [C.POINTER(FusionDesc)]),
-    "tmf_fusion_attn_maps": (_i, [C.POINTER(FusionDesc), _p, _p, C.POINTER(XformerParams), _p, _z, _p, _p, _p, _p]),
-})
-
-
-
-class HeadsDesc(C.Structure):
-    _fields_ = [(n, _i) for n in ("B", "N", "dim", "H1", "H2", "HD", "NC", "training")] + [("momentum", _f * 3), ("eps", _f * 3)]
-
-
-HEADS_PARAMS = ("fc0_w", "fc0_b", "bn1_g", "bn1_b", "fc4_w", "fc4_b", "bn5_g", "bn5_b", "fc8_w", "fc8_b",
-                "d0_w", "d0_b", "dbn_g", "dbn_b", "d3_w", "d3_b")
-HEADS_BUFFERS = ("bn1_rm", "bn1_rv", "bn5_rm", "bn5_rv", "dbn_rm", "dbn_rv")
-
-
-class HeadsParams(C.Structure):
-    _fields_ = [(n, _p) for n in HEADS_PARAMS + HEADS_BUFFERS]
-
-
-class HeadsGrads(C.Structure):
-    _fields_ = [(n, _p) for n in HEADS_PARAMS]
-
-
-PROTOTYPES.update({
-    "tmf_heads_saved_bytes": (_z, [C.POINTER(HeadsDesc)]),
-    "tmf_heads_bwd_scratch_bytes": (_z, [C.POINTER(HeadsDesc)]),
-    "tmf_dropout_keep_masks": (_i, [_i, _p, _p, _p, C.c_ulonglong, C.c_ulonglong, _p]),
-    "tmf_heads_fwd": (_i, [C.POINTER(HeadsDesc), _p, _p, _p, _p, _p, C.POINTER(HeadsParams), _p, _p, _p, _p, _z, _p]),
-    "tmf_heads_bwd": (_i, [C.POINTER(HeadsDesc), _p, _p, _p, C.POINTER(HeadsParams), _p, _z, _p, _p, _p,
-                           C.POINTER(HeadsGrads), _p, _p, _p, _f, _p, _z, _p]),
-    "tmf_adam_state_elems": (_l, [_i, C.POINTER(_l)]),
-    "tmf_adam_step": (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_l), _p, _p, _d, _d, _d, _d, _d, _i, _p]),
-    "tmf_sgd_step": (_i, [_i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_l), _p, C.POINTER(_i), _d, _d, _d, _p]),
-})
-ADAM_MAX_TENSORS = 160
-
-
-class HeadsCnnDesc(C.Structure):
-    _fields_ = [(n, _i) for n in ("B", "N", "dim", "M", "H", "HD", "NC", "training")] + [("momentum", _f), ("eps", _f)]
-
-
-HEADS_CNN_PARAMS = ("fc0_w", "fc0_b", "fc2_w", "fc2_b", "d0_w", "d0_b", "dbn_g", "dbn_b", "d3_w", "d3_b")
-
-
-class HeadsCnnParams(C.Structure):          # field order of tmf_heads_cnn_params (the two running buffers sit ahead of d3_*)
-    _fields_ = [(n, _p) for n in HEADS_CNN_PARAMS[:8] + ("dbn_rm", "dbn_rv") + HEADS_CNN_PARAMS[8:]]
-
-
-class HeadsCnnGrads(C.Structure):
-    _fields_ = [(n, _p) for n in HEADS_CNN_PARAMS]
-
-
-PROTOTYPES.update({
-    "tmf_heads_cnn_saved_bytes": (_z, [C.POINTER(HeadsCnnDesc)]),
-    "tmf_heads_cnn_bwd_scratch_bytes": (_z, [C.POINTER(HeadsCnnDesc)]),
-    "tmf_heads_cnn_fwd": (_i, [C.POINTER(HeadsCnnDesc), _p, _p, C.POINTER(HeadsCnnParams), _p, _p, _p, _p, _z, _p]),
-    "tmf_heads_cnn_bwd": (_i, [C.POINTER(HeadsCnnDesc), C.POINTER(HeadsCnnParams), _p, _z, _p, _p, _p,
-                               C.POINTER(HeadsCnnGrads), _p, _p, _f, _p, _z, _p]),
-})
-
-PROTOTYPES.update({
-    "tmf_faloss_ok": (_i, [_i, _i, _i]),
-    "tmf_faloss_partial_rows": (_i, [_i, _i]),
-    "tmf_faloss_workspace_bytes": (_z, [_i, _i]),
-    "tmf_faloss_fwd": (_i, [_p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
-    "tmf_faloss_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "tmf_supcon_ok": (_i, [_i, _i, _i]),
-    "tmf_supcon_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
-    "tmf_supcon_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-})
-
-PROTOTYPES.update({
-    "tmf_ce_ok": (_i, [_i, _i]),
-    "tmf_ce_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "tmf_ce_bwd": (_i, [_p, _p, _p, _i, _i, _p]),
-    "tmf_adv_criterion_fwd": (_i, [_p] * 9 + [_i, _i, _p]),
-    "tmf_adv_criterion_bwd": (_i, [_p] * 8 + [_i, _i, _p]),
-    "tmf_train_metrics_update": (_i, [_p] * 6 + [_i, _i, _p]),
-    "tmf_eval_metrics_update": (_i, [_p, _p, _p, _l, _p, _p, _i, _i, _p]),
-    "tmf_auc_ok": (_i, [_l]),
-    "tmf_auc_workspace_bytes": (_z, [_l]),
-    "tmf_auc": (_i, [_p, _p, _l, _p, _p, _p]),
-})
-TRAIN_METRICS_WORDS = 8      # the state of tmf_train_metrics_update
+_names = lambda cname: tuple(n for n, _t in STRUCTS[cname]._fields_)
+# the name tuples the ops iterate over, in the structs' own field order
+HEADS_PARAMS = _names("tmf_heads_grads")
+HEADS_BUFFERS = tuple(n for n in _names("tmf_heads_params") if n not in HEADS_PARAMS)
+HEADS_CNN_PARAMS = _names("tmf_heads_cnn_grads")
+XFORMER_PTRS = _names("tmf_xformer_params")[:_names("tmf_xformer_params").index("eps1")]
 
 _lib = None
 

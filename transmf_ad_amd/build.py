@@ -51,9 +51,11 @@ def _read(path):
         return None
 
 
+ABI_HEADER = os.path.join(HERE, "..", "include", "tmf_hip.h")      # the C ABI; _lib.py derives the ctypes binding from it
+
+
 def _headers():
-    return [os.path.join(CSRC, "tmf_common.h"), os.path.join(CSRC, "tmf_device.h"), os.path.join(CSRC, "tmf_optim.h"), os.path.join(CSRC, "conv1_z.h"),
-            os.path.join(HERE, "..", "include", "tmf_hip.h")]
+    return [os.path.join(CSRC, h) for h in ("tmf_common.h", "tmf_device.h", "tmf_optim.h", "conv1_z.h", "xformer_launch.h")] + [ABI_HEADER]
 
 
 def source_digest():

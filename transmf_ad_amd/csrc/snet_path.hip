@@ -23,9 +23,7 @@ struct LayerPlan {
     int cin, cout, k, pool;
     int D, H, W;            // conv input = conv output dims of the block
     int oD, oH, oW;         // block output dims (after the pool)
-    bool bf;                // bf16 matrix-core kernels for this block's conv / dgrad / wgrad
-    bool sp;                // fp32x: forward / data gradient as six bf16 partial products per fp32 product, weight gradient exact fp32
-    bool wgf, wgd, wgw;     // fp32: forward / data gradient / weight gradient in the Winograd form (tmf_set_option("conv_wino", ..), conv3d_wino.hip)
+    int fwd, dgr, wgr;      // TMF_CONV_* family of the forward / data gradient / weight gradient (tmf_conv_block_algo)
     bool x16, z16, o16;     // bf16 storage of the block input, the raw conv output (and dz), the block output
     size_t off_z, off_out, off_vec, off_wf, off_wd;     // in the saved workspace
     bool route;             // max-pooled block, fp32: the forward keeps the pool routing for the backward (option "pool_recompute")
@@ -56,6 +54,99 @@ int check_desc(const char* fn, const tmf_snet_desc* d) {
     return TMF_OK;
 }
 
+// ---- what a block's kernel family (LayerPlan::fwd / dgr / wgr, from tmf_conv_block_algo) means: one switch per question.
+// Blocks 1 .. 6; the first block has its fused passes.  rt_min: TMF_SNET_ALONE's "conv_rt" for the direct kernels.
+
+inline int rt_min_of(const tmf_snet_desc& d) { return (d.flags & TMF_SNET_ALONE) ? 1 : 0; }
+
+// rows of the statistics partials the forward writes
+int stat_rows(const tmf_snet_desc& d, const LayerPlan& L) {
+    switch (L.fwd) {
+    case TMF_CONV_BF16:  return tmf_conv3d_bf16_stat_blocks(d.B, L.D, L.H, L.W);
+    case TMF_CONV_SPLIT: return tmf_conv3d_split_stat_blocks(d.B, L.D, L.H, L.W);
+    case TMF_CONV_WINO:  return tmf_conv3d_wino_stat_blocks(d.B, L.D, L.H, L.W);
+    default:             return tmf_conv3d_stat_blocks_mode(d.B, L.D, L.H, L.W, L.cin, L.cout, L.k, rt_min_of(d));
+    }
+}
+
+size_t wgrad_workspace_bytes(const tmf_snet_desc& d, const LayerPlan& L) {
+    switch (L.wgr) {
+    case TMF_CONV_BF16: return tmf_conv3d_wgrad_bf16_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout);
+    case TMF_CONV_WINO: return tmf_conv3d_wgrad_wino_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout);
+    default:            return tmf_conv3d_wgrad_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout, L.k);
+    }
+}
+
+// bytes of the block's weights in the layout a family reads
+size_t weight_bytes(const LayerPlan& L, int family) {
+    const size_t wn = (size_t)L.k * L.k * L.k * L.cin * L.cout;
+    switch (family) {
+    case TMF_CONV_WINO:  return tmf_conv3d_wino_weight_bytes(L.cin, L.cout);
+    case TMF_CONV_SPLIT: return wn * 6;
+    case TMF_CONV_BF16:  return wn * 2;
+    default:             return wn * 4;
+    }
+}
+
+// Train forward: this step's weights in the forward (wf) and data-gradient (wd) layouts.  The Winograd layouts are not written
+// here (tmf_snet_train_fwd packs those of all blocks in one launch ahead).  For dim % 32 == 0 every channel count past the
+// first block is a multiple of 8, so a bf16 / split forward always comes with the same family's data gradient.
+int pack_weights(const LayerPlan& L, const float* w, void* wf, void* wd, void* stream) {
+    const bool uf = L.fwd == TMF_CONV_WINO, ud = L.dgr == TMF_CONV_WINO;
+    switch (L.fwd) {
+    case TMF_CONV_BF16:  return tmf_pack_conv_weights_bf16(w, wf, wd, L.cout, L.cin, 27, stream);
+    case TMF_CONV_SPLIT: return tmf_pack_conv_weights_split3(w, wf, wd, L.cout, L.cin, 27, stream);
+    default:
+        if (uf && ud) return TMF_OK;
+        return tmf_pack_conv_weights(w, uf ? nullptr : (float*)wf, ud ? nullptr : (float*)wd, L.cout, L.cin, L.k * L.k * L.k, stream);
+    }
+}
+
+// z = conv(x); part (may be NULL): stat_rows() rows of statistics partials
+int launch_fwd(const tmf_snet_desc& d, const LayerPlan& L, const void* x, const void* wf, void* z, float* part, void* stream) {
+    switch (L.fwd) {
+    case TMF_CONV_BF16:
+        return tmf_conv3d_fwd_bf16_t(x, wf, z, part, d.B, L.D, L.H, L.W, L.cin, L.cout, (L.x16 ? 1 : 0) | (L.z16 ? 2 : 0), stream);
+    case TMF_CONV_SPLIT:
+        return tmf_conv3d_fwd_split((const float*)x, wf, (float*)z, part, d.B, L.D, L.H, L.W, L.cin, L.cout, stream);
+    case TMF_CONV_WINO:
+        return tmf_conv3d_fwd_wino((const float*)x, (const float*)wf, (float*)z, part, d.B, L.D, L.H, L.W, L.cin, L.cout, stream);
+    default:
+        return tmf_conv3d_fwd_mode((const float*)x, (const float*)wf, (float*)z, part, d.B, L.D, L.H, L.W, L.cin, L.cout, L.k,
+                                   rt_min_of(d), stream);
+    }
+}
+
+// dx = the forward entries on dz with the data-gradient weights and the channel counts swapped
+int launch_dgrad(const tmf_snet_desc& d, const LayerPlan& L, const void* dz, const void* wd, void* dx, void* stream) {
+    switch (L.dgr) {
+    case TMF_CONV_BF16:
+        return tmf_conv3d_fwd_bf16_t(dz, wd, dx, nullptr, d.B, L.D, L.H, L.W, L.cout, L.cin, (L.z16 ? 1 : 0) | (L.x16 ? 2 : 0), stream);
+    case TMF_CONV_SPLIT:
+        return tmf_conv3d_fwd_split((const float*)dz, wd, (float*)dx, nullptr, d.B, L.D, L.H, L.W, L.cout, L.cin, stream);
+    case TMF_CONV_WINO:
+        return tmf_conv3d_fwd_wino((const float*)dz, (const float*)wd, (float*)dx, nullptr, d.B, L.D, L.H, L.W, L.cout, L.cin, stream);
+    default:
+        return tmf_conv3d_fwd_mode((const float*)dz, (const float*)wd, (float*)dx, nullptr, d.B, L.D, L.H, L.W, L.cout, L.cin, L.k,
+                                   rt_min_of(d), stream);
+    }
+}
+
+// dw in the nn.Conv3d layout
+int launch_wgrad(const tmf_snet_desc& d, const LayerPlan& L, const void* x, const void* dz, float* dw, void* ws, size_t ws_bytes,
+                 void* stream) {
+    switch (L.wgr) {
+    case TMF_CONV_BF16:
+        return tmf_conv3d_wgrad_bf16_t(x, dz, dw, ws, ws_bytes, d.B, L.D, L.H, L.W, L.cin, L.cout, L.x16 ? 1 : 0, TMF_DW_REFERENCE, stream);
+    case TMF_CONV_WINO:
+        return tmf_conv3d_wgrad_wino((const float*)x, (const float*)dz, dw, ws, ws_bytes, d.B, L.D, L.H, L.W, L.cin, L.cout,
+                                     TMF_DW_REFERENCE, stream);
+    default:
+        return tmf_conv3d_wgrad((const float*)x, (const float*)dz, dw, ws, ws_bytes, d.B, L.D, L.H, L.W, L.cin, L.cout, L.k,
+                                TMF_DW_REFERENCE, stream);
+    }
+}
+
 Plan make_plan(const tmf_snet_desc& d, bool train = true) {
     Plan p;
     const int rec = tmf_opt(TMF_OPT_POOL_RECOMPUTE);        // 0 keep the routing, 1 recompute it, 2 / 3: in block 0 / blocks 2, 4 only
@@ -73,21 +164,16 @@ Plan make_plan(const tmf_snet_desc& d, bool train = true) {
         L.D = D; L.H = H; L.W = W;
         if (pool[l] != TMF_POOL_NONE) { D /= 2; H /= 2; W /= 2; }
         L.oD = D; L.oH = H; L.oW = W;
-        L.bf = b16 && ks[l] == 3 && cin[l] > 1 && cin[l] % 8 == 0;
-        // (both channel counts multiples of 8: the data gradient is the same kernel with the roles swapped)
-        L.sp = d.precision == TMF_PREC_FP32X && ks[l] == 3 && cin[l] > 1 && cin[l] % 8 == 0 && cout[l] % 8 == 0;
-        const int wino = (d.precision == TMF_PREC_FP32 && ks[l] == 3 && cin[l] > 1) ? tmf_conv_wino_mode() : 0;
-        L.wgf = wino >= 2 && tmf_conv3d_wino_ok(cin[l], cout[l]);
-        L.wgd = wino >= 1 && tmf_conv3d_wino_ok(cout[l], cin[l]);
-        L.wgw = wino >= 3 && tmf_conv3d_wgrad_wino_ok(cin[l], cout[l]);
+        const int algo = tmf_conv_block_algo(d.precision, cin[l], cout[l], ks[l]);
+        L.fwd = algo & 15; L.dgr = (algo >> 4) & 15; L.wgr = (algo >> 8) & 15;
     }
     for (int l = 0; l < NL; ++l) {
         LayerPlan& L = p.L[l];
         // a block hands a bf16 tensor to the next one iff both run on the bf16 kernels (the first block's fused
         // bf16 passes count): networks.py sNet.forward_channels_last
-        const bool mine = l == 0 ? b16 : L.bf;
-        L.o16 = s16 && l + 1 < NL && mine && p.L[l + 1].bf;
-        L.z16 = s16 && L.bf;
+        const bool mine = l == 0 ? b16 : L.fwd == TMF_CONV_BF16;
+        L.o16 = s16 && l + 1 < NL && mine && p.L[l + 1].fwd == TMF_CONV_BF16;
+        L.z16 = s16 && L.fwd == TMF_CONV_BF16;
         L.x16 = l > 0 && p.L[l - 1].o16;
         const size_t vox = (size_t)d.B * L.D * L.H * L.W, ovox = (size_t)d.B * L.oD * L.oH * L.oW;
         L.x_bytes = vox * L.cin * (L.x16 ? 2 : 4);
@@ -102,10 +188,8 @@ Plan make_plan(const tmf_snet_desc& d, bool train = true) {
         L.off_zsel = off; off += L.route ? up256(ovox * L.cout * 4) : 0;
         L.off_arg = off; off += L.route && l == 0 ? up256(ovox * L.cout) : 0;
         L.off_vec = off; off += (size_t)4 * L.cpad * 4;
-        const size_t wn = (size_t)L.k * L.k * L.k * L.cin * L.cout;
-        const size_t wino_b = tmf_conv3d_wino_weight_bytes(L.cin, L.cout);
-        L.off_wf = off; off += up256(L.wgf ? wino_b : wn * (L.sp ? 6 : L.bf ? 2 : 4));
-        L.off_wd = off; off += l == 0 ? 0 : up256(L.wgd ? wino_b : wn * (L.sp ? 6 : L.bf ? 2 : 4));
+        L.off_wf = off; off += up256(weight_bytes(L, L.fwd));
+        L.off_wd = off; off += l == 0 ? 0 : up256(weight_bytes(L, L.dgr));
         int nblk, nb2;
         size_t ws;
         if (l == 0) {
@@ -120,14 +204,9 @@ Plan make_plan(const tmf_snet_desc& d, bool train = true) {
                 if (wf_ > ws) ws = wf_;
             }
         } else {
-            nblk = L.bf ? tmf_conv3d_bf16_stat_blocks(d.B, L.D, L.H, L.W)
-                   : L.sp ? tmf_conv3d_split_stat_blocks(d.B, L.D, L.H, L.W)
-                   : L.wgf ? tmf_conv3d_wino_stat_blocks(d.B, L.D, L.H, L.W)
-                        : tmf_conv3d_stat_blocks_mode(d.B, L.D, L.H, L.W, L.cin, L.cout, L.k, (d.flags & TMF_SNET_ALONE) ? 1 : 0);
+            nblk = stat_rows(d, L);
             nb2 = tmf_bn_act_pool_bwd_blocks(d.B, L.D, L.H, L.W, L.cout, L.pool);
-            ws = L.bf ? tmf_conv3d_wgrad_bf16_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout)
-                 : L.wgw ? tmf_conv3d_wgrad_wino_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout)
-                      : tmf_conv3d_wgrad_workspace_bytes(d.B, L.D, L.H, L.W, L.cin, L.cout, L.k);
+            ws = wgrad_workspace_bytes(d, L);
         }
         const size_t pb = (size_t)nblk * 2 * L.cout * 4, pb2 = (size_t)nb2 * 2 * L.cout * 4;
         if (pb > part_max) part_max = pb;
@@ -160,6 +239,26 @@ inline Vecs vecs_of(char* base, const LayerPlan& L) {
 }
 
 }  // namespace
+
+// The one rule (include/tmf_hip.h): make_plan above and the Python binding's block-by-block path both ask it.
+extern "C" int tmf_conv_block_algo(int precision, int cin, int cout, int ksize) {
+    if (precision != TMF_PREC_FP32 && precision != TMF_PREC_BF16 && precision != TMF_PREC_FP32X) return -1;
+    int fwd = TMF_CONV_DIRECT, dgr = TMF_CONV_DIRECT, wgr = TMF_CONV_DIRECT;
+    if (ksize == 3 && cin > 1) {
+        if (precision == TMF_PREC_FP32) {
+            const int wino = tmf_opt(TMF_OPT_CONV_WINO);
+            if (wino >= 2 && tmf_conv3d_wino_ok(cin, cout)) fwd = TMF_CONV_WINO;
+            if (wino >= 1 && tmf_conv3d_wino_ok(cout, cin)) dgr = TMF_CONV_WINO;
+            if (wino >= 3 && tmf_conv3d_wgrad_wino_ok(cin, cout)) wgr = TMF_CONV_WINO;
+        } else if (cin % 8 == 0) {
+            // the data gradient is the forward kernel with the channel roles swapped: it wants cout in 8-channel groups too
+            fwd = precision == TMF_PREC_BF16 ? TMF_CONV_BF16 : TMF_CONV_SPLIT;
+            if (cout % 8 == 0) dgr = fwd;
+            if (precision == TMF_PREC_BF16) wgr = TMF_CONV_BF16;
+        }
+    }
+    return fwd | (dgr << 4) | (wgr << 8);
+}
 
 extern "C" size_t tmf_snet_saved_bytes(const tmf_snet_desc* d) {
     if (check_desc("tmf_snet_saved_bytes", d) != TMF_OK) return 0;
@@ -195,8 +294,9 @@ extern "C" int tmf_snet_train_fwd(const tmf_snet_desc* d, const float* vol, cons
         int n = 0;
         for (int l = 0; l < NL; ++l) {
             const LayerPlan& L = p.L[l];
-            if (l == 0 || L.bf || L.sp || !(L.wgf || L.wgd)) continue;
-            pw[n] = prm->weight[l]; pf[n] = L.wgf ? (float*)(base + L.off_wf) : nullptr; pd[n] = L.wgd ? (float*)(base + L.off_wd) : nullptr;
+            const bool uf = L.fwd == TMF_CONV_WINO, ud = L.dgr == TMF_CONV_WINO;
+            if (!(uf || ud)) continue;
+            pw[n] = prm->weight[l]; pf[n] = uf ? (float*)(base + L.off_wf) : nullptr; pd[n] = ud ? (float*)(base + L.off_wd) : nullptr;
             pco[n] = L.cout; pci[n] = L.cin; ++n;
         }
         if (n > 0) TMF_TRY(tmf_pack_conv_weights_wino_multi(n, pw, pf, pd, pco, pci, stream));
@@ -224,28 +324,10 @@ extern "C" int tmf_snet_train_fwd(const tmf_snet_desc* d, const float* vol, cons
                 nblk = 2;
             } else if (b16) TMF_TRY(tmf_c1_stats_bf16(vol, (const float*)wf, part, d->B, L.D, L.H, L.W, L.cout, stream));
             else     TMF_TRY(tmf_c1_stats(vol, (const float*)wf, part, d->B, L.D, L.H, L.W, L.cout, stream));
-        } else if (L.bf) {
-            TMF_TRY(tmf_pack_conv_weights_bf16(prm->weight[l], wf, wd, L.cout, L.cin, 27, stream));
-            nblk = tmf_conv3d_bf16_stat_blocks(d->B, L.D, L.H, L.W);
-            TMF_TRY(tmf_conv3d_fwd_bf16_t(x, wf, z, part, d->B, L.D, L.H, L.W, L.cin, L.cout,
-                                          (L.x16 ? 1 : 0) | (L.z16 ? 2 : 0), stream));
-        } else if (L.sp) {
-            TMF_TRY(tmf_pack_conv_weights_split3(prm->weight[l], wf, wd, L.cout, L.cin, 27, stream));
-            nblk = tmf_conv3d_split_stat_blocks(d->B, L.D, L.H, L.W);
-            TMF_TRY(tmf_conv3d_fwd_split((const float*)x, wf, (float*)z, part, d->B, L.D, L.H, L.W, L.cin, L.cout, stream));
         } else {
-            if (!L.wgf || !L.wgd)                           // (the Winograd layouts of this block: packed above, all blocks in one launch)
-                TMF_TRY(tmf_pack_conv_weights(prm->weight[l], L.wgf ? nullptr : (float*)wf, L.wgd ? nullptr : (float*)wd, L.cout,
-                                              L.cin, L.k * L.k * L.k, stream));
-            if (L.wgf) {
-                nblk = tmf_conv3d_wino_stat_blocks(d->B, L.D, L.H, L.W);
-                TMF_TRY(tmf_conv3d_fwd_wino((const float*)x, (const float*)wf, (float*)z, part, d->B, L.D, L.H, L.W, L.cin, L.cout, stream));
-            } else {
-                const int rt_min = (d->flags & TMF_SNET_ALONE) ? 1 : 0;
-                nblk = tmf_conv3d_stat_blocks_mode(d->B, L.D, L.H, L.W, L.cin, L.cout, L.k, rt_min);
-                TMF_TRY(tmf_conv3d_fwd_mode((const float*)x, (const float*)wf, (float*)z, part, d->B, L.D, L.H, L.W, L.cin, L.cout,
-                                            L.k, rt_min, stream));
-            }
+            TMF_TRY(pack_weights(L, prm->weight[l], wf, wd, stream));
+            nblk = stat_rows(*d, L);
+            TMF_TRY(launch_fwd(*d, L, x, wf, z, part, stream));
         }
         TMF_TRY(tmf_bn_finalize(part, nblk, L.cout, count, prm->gamma[l], prm->beta[l], prm->bias[l], prm->running_mean[l],
                                 prm->running_var[l], d->momentum[l], d->eps[l], v.mean, v.invstd, v.scale, v.shift, stream));
@@ -307,10 +389,13 @@ extern "C" int tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const
         const Vecs v = vecs_of(base, L);
         void* o = l == NL - 1 ? (void*)out : (void*)(base + L.off_out);
         void* wf = base + L.off_wf;
-        const bool wino = L.wgf && L.pool != TMF_POOL_AVG2;       // the Winograd form of the one-kernel block (fp32 only: make_plan)
-        if (L.bf) TMF_TRY(tmf_pack_conv_weights_bf16(prm->weight[l], wf, nullptr, L.cout, L.cin, 27, stream));
-        else if (wino) TMF_TRY(tmf_pack_conv_weights_wino(prm->weight[l], (float*)wf, nullptr, L.cout, L.cin, stream));
-        else TMF_TRY(tmf_pack_conv_weights(prm->weight[l], (float*)wf, nullptr, L.cout, L.cin, L.k * L.k * L.k, stream));
+        // the forward's family; the Winograd form of the one-kernel block has no average pool
+        const int fam = (L.fwd == TMF_CONV_WINO && L.pool == TMF_POOL_AVG2) ? TMF_CONV_DIRECT : L.fwd;
+        switch (fam) {
+        case TMF_CONV_BF16: TMF_TRY(tmf_pack_conv_weights_bf16(prm->weight[l], wf, nullptr, L.cout, L.cin, 27, stream)); break;
+        case TMF_CONV_WINO: TMF_TRY(tmf_pack_conv_weights_wino(prm->weight[l], (float*)wf, nullptr, L.cout, L.cin, stream)); break;
+        default:            TMF_TRY(tmf_pack_conv_weights(prm->weight[l], (float*)wf, nullptr, L.cout, L.cin, L.k * L.k * L.k, stream));
+        }
         TMF_TRY(tmf_bn_eval_coeffs(prm->gamma[l], prm->beta[l], prm->bias[l], prm->running_mean[l], prm->running_var[l],
                                    d->eps[l], L.cout, v.scale, v.shift, stream));
         if ((size_t)L.oD * L.oH * L.oW == 0) continue;
@@ -319,17 +404,13 @@ extern "C" int tmf_snet_eval_fwd(const tmf_snet_desc* d, const float* vol, const
                                                      d->slope[l], L.o16 ? 1 : 0, stream));
             else     TMF_TRY(tmf_c1_bn_pool_fwd(vol, (const float*)wf, v.scale, v.shift, (float*)o, d->B, L.D, L.H, L.W, L.cout,
                                                 d->slope[l], stream));
-        } else if (L.bf) {
+        } else if (b16) {       // two kernels; a block the bf16 kernels do not take (the 1x1x1 layer) runs them in fp32
             void* z = base + L.off_z;
-            TMF_TRY(tmf_conv3d_fwd_bf16_t(x, wf, z, nullptr, d->B, L.D, L.H, L.W, L.cin, L.cout,
-                                          (L.x16 ? 1 : 0) | (L.z16 ? 2 : 0), stream));
+            if (fam == TMF_CONV_BF16) TMF_TRY(launch_fwd(*d, L, x, wf, z, nullptr, stream));
+            else TMF_TRY(tmf_conv3d_fwd((const float*)x, (const float*)wf, (float*)z, nullptr, d->B, L.D, L.H, L.W, L.cin, L.cout, L.k, stream));
             TMF_TRY(tmf_bn_act_pool_fwd_t(z, v.scale, v.shift, o, d->B, L.D, L.H, L.W, L.cout, L.pool, d->slope[l],
                                           (L.z16 ? 1 : 0) | (L.o16 ? 2 : 0), stream));
-        } else if (b16) {       // a block the bf16 kernels do not take (the 1x1x1 layer) inside a bf16 encoder: two kernels, fp32
-            float* z = (float*)(base + L.off_z);
-            TMF_TRY(tmf_conv3d_fwd((const float*)x, (const float*)wf, z, nullptr, d->B, L.D, L.H, L.W, L.cin, L.cout, L.k, stream));
-            TMF_TRY(tmf_bn_act_pool_fwd_t(z, v.scale, v.shift, o, d->B, L.D, L.H, L.W, L.cout, L.pool, d->slope[l], 0, stream));
-        } else if (wino) {
+        } else if (fam == TMF_CONV_WINO) {
             TMF_TRY(tmf_conv3d_fwd_wino_affine((const float*)x, (const float*)wf, v.scale, v.shift, (float*)o, d->B, L.D, L.H, L.W,
                                                L.cin, L.cout, L.pool, d->slope[l], stream));
         } else {
@@ -455,25 +536,8 @@ extern "C" int tmf_snet_train_bwd_input(const tmf_snet_desc* d, const float* vol
         TMF_TRY(tmf_bn_act_pool_bwd_apply_t(z, go, v.scale, v.shift, v.mean, v.invstd, coef, dz, d->B, L.D, L.H, L.W, L.cout,
                                             L.pool, d->slope[l], io, stream));
         void* dx = sc + ((l & 1) ? p.off_gA : p.off_gB);
-        if (L.bf) {
-            if (g->dweight[l] != nullptr)
-                TMF_TRY(tmf_conv3d_wgrad_bf16_t(x, dz, g->dweight[l], ws, p.ws_bytes, d->B, L.D, L.H, L.W, L.cin, L.cout,
-                                                L.x16 ? 1 : 0, TMF_DW_REFERENCE, stream));
-            TMF_TRY(tmf_conv3d_fwd_bf16_t(dz, wd, dx, nullptr, d->B, L.D, L.H, L.W, L.cout, L.cin,
-                                          (L.z16 ? 1 : 0) | (L.x16 ? 2 : 0), stream));
-        } else {
-            if (g->dweight[l] != nullptr) {
-                if (L.wgw) TMF_TRY(tmf_conv3d_wgrad_wino((const float*)x, (const float*)dz, g->dweight[l], ws, p.ws_bytes, d->B, L.D, L.H,
-                                                         L.W, L.cin, L.cout, TMF_DW_REFERENCE, stream));
-                else TMF_TRY(tmf_conv3d_wgrad((const float*)x, (const float*)dz, g->dweight[l], ws, p.ws_bytes, d->B, L.D, L.H, L.W,
-                                              L.cin, L.cout, L.k, TMF_DW_REFERENCE, stream));
-            }
-            if (L.sp) TMF_TRY(tmf_conv3d_fwd_split((const float*)dz, wd, (float*)dx, nullptr, d->B, L.D, L.H, L.W, L.cout, L.cin, stream));
-            else if (L.wgd) TMF_TRY(tmf_conv3d_fwd_wino((const float*)dz, (const float*)wd, (float*)dx, nullptr, d->B, L.D, L.H, L.W,
-                                                        L.cout, L.cin, stream));
-            else TMF_TRY(tmf_conv3d_fwd_mode((const float*)dz, (const float*)wd, (float*)dx, nullptr, d->B, L.D, L.H, L.W, L.cout,
-                                             L.cin, L.k, (d->flags & TMF_SNET_ALONE) ? 1 : 0, stream));
-        }
+        if (g->dweight[l] != nullptr) TMF_TRY(launch_wgrad(*d, L, x, dz, g->dweight[l], ws, p.ws_bytes, stream));
+        TMF_TRY(launch_dgrad(*d, L, dz, wd, dx, stream));
         go = dx;
         if (l == TMF_SNET_DEEP_FROM && g->deep_event != nullptr) {       // blocks 6 .. l: every gradient is queued behind this point
             hipError_t e = hipEventRecord((hipEvent_t)g->deep_event, s);

@@ -48,6 +48,7 @@
 // after GELU, after the second Linear), already scaled by 1 / (1 - p), are INPUTS (NULL = inactive) — the random draw
 // stays with the caller, as in heads.hip.
 #include "tmf_device.h"
+#include "xformer_launch.h"
 
 namespace {
 
@@ -1334,7 +1335,7 @@ constexpr size_t XF_BWDKV_LDS = (size_t)(XT * XKP) * 4;
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side: launchers used by fusion_path.hip (C++ linkage, declared there)
+// host side: launchers used by fusion_path.hip (C++ linkage, declared in xformer_launch.h)
 // ---------------------------------------------------------------------------------------------------------------------
 static unsigned long long* g_xf_trace[3] = {nullptr, nullptr, nullptr};
 // debugging hook (tools/xf_trace.py): per-wave phase time stamps of the fused kernels, [workgroups][4 waves][16] uint64 each
@@ -1388,11 +1389,6 @@ int tmf_xf_launch_pack(int n_inst, const tmf_xformer_params* inst, float* const*
     return TMF_OK;
 }
 
-struct tmf_xf_fwd_io {
-    const float *x, *KR, *VC, *pk, *pkv_next, *mask_o, *mask_g, *mask_f;      // pk: this instance's forward pack buffer
-    float *a, *QR, *QC, *out, *lse, *x1, *f, *h, *g, *x2, *y, *m1, *r1, *m2, *r2, *mf, *rf, *KRn, *KCn, *VRn, *VCn;
-};
-
 // infer != 0: the forward-only instances (the io's saved-for-backward pointers, KCn and VRn are not looked at)
 int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fwd_io* io, float scale, int only_kv, int h2,
                       int infer, hipStream_t s) {
@@ -1432,13 +1428,6 @@ int tmf_xf_launch_fwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_fw
 #undef XF_LAUNCH
     return tmf_launch_result(what);
 }
-
-struct tmf_xf_bwd_io {
-    const float *dy, *x, *KR, *KC, *VR, *pk, *mask_o, *mask_g, *mask_f;        // pk: this instance's backward pack buffer
-    const float *QR, *QC, *out, *lse, *x1, *h, *x2, *m1, *r1, *m2, *r2, *mf, *rf;
-    float *dx2, *dh, *dx1, *dq, *DR, *DC, *delta, *dx, *part, *dkv, *dctx;
-    const float* dctx_acc;
-};
 
 int tmf_xf_launch_bwd(int B, int N, const tmf_xformer_params* w, const tmf_xf_bwd_io* io, float scale, int h2, hipStream_t s) {
     int rc;

@@ -123,9 +123,17 @@ def activation_storage_bf16(precision=None) -> bool:
     return resolve_precision(precision)[1]
 
 
+def conv_block_algo(mode: str, cin: int, cout: int, k: int):
+    """(forward, data gradient, weight gradient) kernel family, each a _lib.CONV_* code, of one encoder block in conv precision
+    `mode` under the options of the moment: the library's one rule (tmf_conv_block_algo), the same the whole-encoder path
+    plans with — so the block-by-block path and the one-call path run the same kernels."""
+    a = _lib.query("tmf_conv_block_algo", _lib.PRECISION[mode], cin, cout, k)
+    return a & 15, (a >> 4) & 15, (a >> 8) & 15
+
+
 def bf16_conv_capable(cin: int, k: int) -> bool:
-    """the 3x3x3 bf16 matrix-core kernels need 8-channel input groups"""
-    return k == 3 and cin > 1 and cin % 8 == 0
+    """the 3x3x3 bf16 matrix-core kernels need 8-channel input groups (the forward's family does not depend on cout)"""
+    return conv_block_algo("bf16", cin, cin, k)[0] == _lib.CONV_BF16
 
 
 def pack_weight_bf16(weight: torch.Tensor) -> torch.Tensor:
@@ -322,19 +330,17 @@ class ConvBnActPool(torch.autograd.Function):
         if C != cin:
             raise _lib.TmfError(f"conv expects {cin} input channels, got {C}")
         weight = _chk(weight, "weight")
-        bf16 = mode if (mode != "fp32" and k == 3 and cin % 8 == 0 and cin > 1) else False
+        # the kernel family per direction: the same choice as the whole-encoder path (snet_path.hip make_plan asks the same
+        # query), so the two stay bit-identical
+        fam_f, fam_d, fam_w = ctx.fam = conv_block_algo(mode, cin, cout, k)
+        bf16 = {_lib.CONV_BF16: "bf16", _lib.CONV_SPLIT: "fp32x"}.get(fam_f, False)
         z16 = bf16 == "bf16" and act16           # raw conv output (and dz) stored as bf16
         if x.dtype == _b16 and bf16 != "bf16":
             x = x.float()                         # only the bf16 kernels read bf16 tensors
         if out_bf16 and not z16:
             raise _lib.TmfError("a bf16 block output needs conv precision 'bf16' with bf16 activation storage")
         wf = wd = None
-        # Winograd form of the fp32 products (tmf_set_option("conv_wino", ..)): the same choice per layer and
-        # direction as the whole-encoder path (snet_path.hip make_plan), so the two stay bit-identical
-        wino = conv_wino_mode() if (not bf16 and k == 3 and cin > 1) else 0
-        wino_f = wino >= 2 and wino_ok(cin, cout)
-        wino_d = wino >= 1 and wino_ok(cout, cin)
-        ctx.wino_w = wino >= 3 and wgrad_wino_ok(cin, cout)
+        wino_f, wino_d = fam_f == _lib.CONV_WINO, fam_d == _lib.CONV_WINO       # (tmf_set_option("conv_wino", ..))
         if not bf16:                      # both weight layouts in one launch; the dgrad one is kept for backward
             want_d = ctx.needs_input_grad[0]
             wf, wd = pack_weights_both(weight, want_d and not wino_d, want_fwd=not wino_f)
@@ -343,11 +349,9 @@ class ConvBnActPool(torch.autograd.Function):
                 wf = uf if wino_f else wf
                 wd = ud if (wino_d and want_d) else wd
         elif bf16 == "bf16":
-            wf, wd = pack_weights_both_bf16(weight, ctx.needs_input_grad[0] and cout % 8 == 0)
-        elif ctx.needs_input_grad[0] and cout % 8 == 0:      # fp32x: both split layouts in one launch
-            wf, wd = pack_weights_split3(weight, True)
-        else:
-            wf, wd = pack_weights_split3(weight, False)
+            wf, wd = pack_weights_both_bf16(weight, ctx.needs_input_grad[0] and fam_d == _lib.CONV_BF16)
+        else:                             # fp32x: both split layouts in one launch
+            wf, wd = pack_weights_split3(weight, ctx.needs_input_grad[0] and fam_d == _lib.CONV_SPLIT)
 
         def conv(stats):
             if bf16 == "bf16":
@@ -389,9 +393,7 @@ class ConvBnActPool(torch.autograd.Function):
                       B, D, H, W, cout, pc, float(slope), io, s)
         ctx.save_for_backward(x, weight if wd is None else wd, z, scale, shift, mean, invstd)
         ctx.cfg = (training, float(slope), pc, cin, cout, k, bias is not None)
-        ctx.bf16 = bf16
         ctx.packed_dgrad = wd is not None
-        ctx.wino_d = bool(wino_d and wd is not None)
         ctx.io = io
         return out
 
@@ -423,21 +425,22 @@ class ConvBnActPool(torch.autograd.Function):
         dz = torch.empty_like(z)
         _lib.call("tmf_bn_act_pool_bwd_apply_t", z.data_ptr(), dout.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                   mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(), dz.data_ptr(), B, D, H, W, cout, pc, slope, io, s)
+        _fam_f, fam_d, fam_w = ctx.fam
         dweight = None
         if ctx.needs_input_grad[1]:
-            if ctx.bf16 == "bf16":
+            if fam_w == _lib.CONV_BF16:
                 dweight = conv3d_wgrad_bf16(x, dz, cin, cout, reference_layout=True)
-            elif ctx.wino_w:
+            elif fam_w == _lib.CONV_WINO:
                 dweight = conv3d_wgrad_wino(x, dz, cin, cout, reference_layout=True)
             else:
                 dweight = conv3d_wgrad(x, dz, cin, cout, k, reference_layout=True)
         dx = None
         if ctx.needs_input_grad[0]:
-            if ctx.bf16 == "bf16" and cout % 8 == 0:
+            if fam_d == _lib.CONV_BF16:
                 dx, _, _ = conv3d_bf16_raw(dz, weight, cout, cin, False, out_bf16=x.dtype == _b16)    # weight = packed wd
-            elif ctx.bf16 == "fp32x" and cout % 8 == 0:
+            elif fam_d == _lib.CONV_SPLIT:
                 dx, _, _ = conv3d_split_raw(dz, weight, cout, cin, False)             # weight = packed split wd
-            elif ctx.wino_d:
+            elif fam_d == _lib.CONV_WINO:
                 dx, _, _ = conv3d_wino_raw(dz, weight, cout, cin, False)              # weight = packed Winograd u_dgrad
             else:
                 dzf = dz if dz.dtype == _f32 else dz.float()
@@ -585,7 +588,7 @@ def conv_bn_act_pool_eval_fused(x, weight, bias, gamma, beta, running_mean, runn
     shape = (B, D, H, W, cout) if pc == _lib.POOL_NONE else (B, D // 2, H // 2, W // 2, cout)
     out = torch.empty(shape, device=dev, dtype=_f32)
     if out.numel() > 0:
-        if k == 3 and conv_wino_mode() >= 2 and wino_ok(cin, cout) and pool != "avg":       # as tmf_snet_eval_fwd chooses
+        if conv_block_algo("fp32", cin, cout, k)[0] == _lib.CONV_WINO and pool != "avg":    # as tmf_snet_eval_fwd chooses
             uf, _ = pack_weights_wino(weight, True, False)
             _lib.call("tmf_conv3d_fwd_wino_affine", x.data_ptr(), uf.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                       out.data_ptr(), B, D, H, W, cin, cout, pc, float(slope), s)
@@ -642,7 +645,7 @@ def snet_eval_one_call(vol, dim, eps, slope, blocks, precision=None, algo=None):
     vol = _chk(vol, "vol")
     B, _, D, H, W = vol.shape
     mode, act16 = resolve_precision(precision)
-    desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision={"fp32": 0, "bf16": 1}[mode], storage_bf16=int(act16),
+    desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision=_lib.PRECISION[mode], storage_bf16=int(act16),
                          flags=snet_algo_flags(algo))
     prm = _lib.SnetParams()
     for l, (w, b, g, be, rm, rv) in enumerate(blocks):
@@ -701,16 +704,18 @@ def snet_algo_flags(algo=None) -> int:
         if "conv_wino" in algo:
             if algo["conv_wino"] not in (0, 1, 2, 3):
                 raise ValueError("conv_wino must be 0, 1, 2 or 3")
-            f = (f & ~(3 << 9)) | (int(algo["conv_wino"]) << 9)
-        for key, bit in (("wino_p", 0x800), ("wino_x", 0x1000), ("c1_gram", 0x2000), ("c1_split", 0x8000)):
+            f = (f & ~_lib.snet_algo_wino(3)) | _lib.snet_algo_wino(int(algo["conv_wino"]))
+        for key, bit in (("wino_p", _lib.SNET_ALGO_WINO_P), ("wino_x", _lib.SNET_ALGO_WINO_X), ("c1_gram", _lib.SNET_ALGO_C1_GRAM),
+                         ("c1_split", _lib.SNET_ALGO_C1_SPLIT)):
             if key in algo:
                 f = (f | bit) if algo[key] else (f & ~bit)
         if "c1_gram" in algo:                            # 2: the bf16 mode's first block through the Gram matrix as well
-            f = (f | 0x4000) if algo["c1_gram"] == 2 else (f & ~0x4000)
+            f = (f | _lib.SNET_ALGO_C1_GRAM_BF16) if algo["c1_gram"] == 2 else (f & ~_lib.SNET_ALGO_C1_GRAM_BF16)
         if "pool_recompute" in algo:                     # 1: the pool routing recomputed in backward; 2 / 3: in block 0 / blocks 2, 4 only
             if algo["pool_recompute"] not in (0, 1, 2, 3):
                 raise ValueError("pool_recompute must be 0, 1, 2 or 3")
-            f = (f & ~0x30000) | {0: 0, 1: 0x30000, 2: 0x10000, 3: 0x20000}[int(algo["pool_recompute"])]
+            c1, bn = _lib.SNET_ALGO_POOL_REC_C1, _lib.SNET_ALGO_POOL_REC_BN
+            f = (f & ~(c1 | bn)) | {0: 0, 1: c1 | bn, 2: c1, 3: bn}[int(algo["pool_recompute"])]
     return f
 
 
@@ -727,10 +732,10 @@ class SNetTrain(torch.autograd.Function):
         dim, momentum, eps, slope = cfg[:4]
         mode, act16 = resolve_precision(cfg[4] if len(cfg) > 4 else None)
         B, _, D, H, W = vol.shape
-        desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision={"fp32": 0, "bf16": 1, "fp32x": 2}[mode], storage_bf16=int(act16),
+        desc = _lib.SnetDesc(B=B, D=D, H=H, W=W, dim=dim, precision=_lib.PRECISION[mode], storage_bf16=int(act16),
                              flags=(_lib.SNET_ALONE if (len(cfg) > 5 and cfg[5]) else 0) | snet_algo_flags(cfg[6] if len(cfg) > 6 else None))
         if not any(ctx.needs_input_grad):
-            desc.flags |= 0x30000              # no backward will follow (no_grad, frozen encoder): keep no pool routing in `saved`
+            desc.flags |= _lib.SNET_ALGO_POOL_REC_C1 | _lib.SNET_ALGO_POOL_REC_BN   # no backward will follow (no_grad, frozen encoder): keep no pool routing in `saved`
         prm = _lib.SnetParams()
         for l in range(7):
             desc.momentum[l], desc.eps[l], desc.slope[l] = momentum[l], eps[l], slope[l]
