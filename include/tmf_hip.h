@@ -935,6 +935,28 @@ int    tmf_auc_ok(long n);
 size_t tmf_auc_workspace_bytes(long n);
 int    tmf_auc(const float* scores, const long long* labels, long n, void* workspace, void* out, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Class activation maps at an encoder block (csrc/cam.hip): act = the block's channels-last output A[B][V][C] (V = d*h*w),
+ * grad = d score / d A, same layout.
+ *   TMF_CAM_GRAD  (Grad-CAM):  w[b][c] = (1/V) sum_v grad[b][v][c],  cam[b][v] = sum_c w[b][c] act[b][v][c]
+ *   TMF_CAM_HIRES (HiResCAM):  cam[b][v] = sum_c grad[b][v][c] act[b][v][c]
+ * flags: TMF_CAM_RELU clamps the map at 0; TMF_CAM_NORMALIZE then divides each sample's map by its maximum — a sample
+ * whose maximum is <= 0 comes out as zeros, never NaN or Inf.
+ * cam [B][V]; weights [B][C] (TMF_CAM_GRAD only) or NULL; peak [B] = each sample's maximum before the division (after the
+ * clamp) or NULL.  cam may be NULL when weights is not (the weights alone; peak then NULL).  act, grad and workspace are
+ * 16-byte aligned.  C: tmf_cam_ok = a multiple of 4 in 8..512; any B, V >= 1.  act and grad are read once (grad's
+ * Grad-CAM pass reads grad only, the map pass act only), 16 bytes per lane; no atomics: per-workgroup partials in
+ * `workspace` (tmf_cam_workspace_bytes, 0 for a shape tmf_cam refuses) combined in a fixed order — two calls give the same
+ * bits.  Launches: 3 (Grad: column sums, map, normalise) or 2 (HiRes); the last one only with TMF_CAM_NORMALIZE or peak. */
+#define TMF_CAM_GRAD      0
+#define TMF_CAM_HIRES     1
+#define TMF_CAM_RELU      1
+#define TMF_CAM_NORMALIZE 2
+int    tmf_cam_ok(int C);
+size_t tmf_cam_workspace_bytes(int B, long V, int C, int method);
+int    tmf_cam(const float* act, const float* grad, float* cam, float* weights, float* peak, void* workspace,
+               size_t workspace_bytes, int B, long V, int C, int method, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

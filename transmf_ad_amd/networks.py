@@ -71,6 +71,16 @@ class sNet(nn.Module):
         self.tmf_precision = None           # None: follow the process default (ops.set_conv_precision / set_activation_storage)
         self.tmf_alone = False              # True: nothing runs beside this encoder (model_single): tmf_snet_desc.flags = TMF_SNET_ALONE
         self.tmf_algo = None                # None: the process options; a dict: this encoder's own kernels (set_algorithm)
+        self.tmf_tap = None                 # None, or a callable (block index, channels-last block output): see TAP_LAYERS
+
+    # tmf_tap: the encoder's feature maps for whoever needs them (gradcam.py).  The Sequentials below are parameter holders —
+    # forward hooks on them never fire, and the one-call paths keep the activations inside a library workspace — so with a
+    # callable here forward_channels_last skips both one-call paths, walks the blocks one by one (bit-identical to the one-call
+    # paths, BatchNorm buffers included) and calls tmf_tap(n, x) on the (B, d, h, w, C) output of each of the seven blocks.
+    # TAP_LAYERS names them by the reference's module paths: a forward hook on the reference's `conv3` / `conv3[2]` sees the
+    # tensor of "conv3" / "conv3.2" (there as (B, C, d, h, w)).  The blocks ahead of a pool (0, 2, 4, 6) are fused with it and
+    # never store their pre-pool activations, so `conv1[2]`, `conv2[5]`, `conv3[5]` and `conv4[5]` are not offered.
+    TAP_LAYERS = {"conv1": 0, "conv2.2": 1, "conv2": 2, "conv3.2": 3, "conv3": 4, "conv4.2": 5, "conv4": 6}
 
     def set_precision(self, conv="fp32", storage="fp32"):
         """Precision of THIS encoder's convolution products ("fp32" | "bf16" | "fp32x") and of the activations between its
@@ -99,7 +109,8 @@ class sNet(nn.Module):
                 torch._foreach_add_(nbt, 1)
         blocks = [(getattr(self, n)[i], getattr(self, n)[i + 1], getattr(self, n)[i + 2]) for n, i, _ in self._PLAN]
         prec = ops.resolve_precision(self.tmf_precision)
-        if (not self.training and not torch.is_grad_enabled() and prec[0] in ("fp32", "bf16") and ops.FUSE_EVAL_BLOCKS
+        tap = getattr(self, "tmf_tap", None)    # a tap: block by block, the one-call paths keep their activations to themselves
+        if (tap is None and not self.training and not torch.is_grad_enabled() and prec[0] in ("fp32", "bf16") and ops.FUSE_EVAL_BLOCKS
                 and all(bn.track_running_stats for _c, bn, _a in blocks)
                 and self._one_call_ok(vol, blocks, eval_mode=True, prec=prec)):
             return ops.snet_eval_one_call(
@@ -107,7 +118,7 @@ class sNet(nn.Module):
                 tuple(float(a.negative_slope) for _c, _b, a in blocks),
                 [(c.weight, c.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var) for c, bn, _a in blocks], prec,
                 getattr(self, "tmf_algo", None))
-        if self._one_call_ok(vol, blocks, prec=prec):
+        if tap is None and self._one_call_ok(vol, blocks, prec=prec):
             params, buffers = [], []
             for conv, bn, _act in blocks:
                 params += [conv.weight, conv.bias, bn.weight, bn.bias]
@@ -134,6 +145,8 @@ class sNet(nn.Module):
                                      bn.running_var, self.training or not bn.track_running_stats,
                                      momentum=momentum, eps=bn.eps, slope=act.negative_slope, pool=pool,
                                      out_bf16=out16, precision=prec)
+            if tap is not None:
+                tap(n_blk, x)
         return x                                 # (B, d, h, w, dim)
 
     def _one_call_ok(self, vol, blocks, eval_mode=False, prec=None):

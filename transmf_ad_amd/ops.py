@@ -1303,6 +1303,41 @@ def fusion_attn_maps(mri_tok, pet_tok, cfg, params, want_probs):
     return cls, recv, probs
 
 
+CAM_METHODS = {"gradcam": _lib.CAM_GRAD, "hirescam": _lib.CAM_HIRES}
+
+
+def cam_ok(act, grad):
+    """tmf_cam takes this pair: float32 tensors on one HIP device, a channel count tmf_cam_ok accepts, at least one voxel."""
+    return (act.is_cuda and grad.is_cuda and act.device == grad.device and act.dtype == _f32 and grad.dtype == _f32
+            and act.numel() > 0 and bool(_lib.query("tmf_cam_ok", int(act.shape[-1]))))
+
+
+def cam(act, grad, method="gradcam", relu=True, normalize=True):
+    """Class activation map of a channels-last activation act (B, ..., C) and the score's gradient by it, same shape
+    (tmf_cam, csrc/cam.hip) -> (cam (B, ...), weights (B, C) or None for "hirescam", peak (B,) = each sample's maximum before
+    the division).  "gradcam": weights = the mean of grad over the voxels, cam = sum_c weights * act; "hirescam": cam =
+    sum_c grad * act.  relu clamps at 0; normalize divides each sample by its maximum (zeros where that is <= 0)."""
+    if method not in CAM_METHODS:
+        raise ValueError(f"method must be one of {sorted(CAM_METHODS)}, got {method!r}")
+    act, grad = _chk(act, "act"), _chk(grad, "grad")
+    if act.shape != grad.shape or act.dim() < 3:
+        raise _lib.TmfError(f"cam shapes: act {tuple(act.shape)} grad {tuple(grad.shape)}")
+    B, C = act.shape[0], act.shape[-1]
+    V = act.numel() // (B * C) if B * C else 0
+    code = CAM_METHODS[method]
+    nws = _lib.query("tmf_cam_workspace_bytes", B, V, C, code)
+    if nws == 0:
+        raise _lib.TmfError(f"tmf_cam takes no activation of shape {tuple(act.shape)} (C a multiple of 4 in 8..512)")
+    ws = torch.empty(nws, device=act.device, dtype=torch.uint8)
+    out = torch.empty(act.shape[:-1], device=act.device, dtype=_f32)
+    weights = torch.empty((B, C), device=act.device, dtype=_f32) if code == _lib.CAM_GRAD else None
+    peak = torch.empty((B,), device=act.device, dtype=_f32)
+    flags = (_lib.CAM_RELU if relu else 0) | (_lib.CAM_NORMALIZE if normalize else 0)
+    _lib.call("tmf_cam", act.data_ptr(), grad.data_ptr(), out.data_ptr(), _ptr(weights), peak.data_ptr(), ws.data_ptr(), nws,
+              B, V, C, code, flags, _stream())
+    return out, weights, peak
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
