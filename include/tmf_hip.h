@@ -957,6 +957,41 @@ size_t tmf_cam_workspace_bytes(int B, long V, int C, int method);
 int    tmf_cam(const float* act, const float* grad, float* cam, float* weights, float* peak, void* workspace,
                size_t workspace_bytes, int B, long V, int C, int method, int flags, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Occlusion sensitivity (csrc/occlusion.hip): blank a region of a volume, run the network again, record how far the class
+ * score falls.  The reference has no such function; these entries replace the loop its user writes around the deployed
+ * model: `for w in windows: x = vol.clone(); x[..., z0:z1, y0:y1, x0:x1] = fill; drop[w] = base - score(model(x))` and, for
+ * the voxel map, `for w in windows: acc[..., z0:z1, y0:y1, x0:x1] += drop[w]; cnt[z0:z1, y0:y1, x0:x1] += 1; acc / cnt`.
+ *
+ * Window grid.  Per axis with extent S, patch p and stride s, 1 <= s <= p: n = ceil(max(S - p, 0) / s) + 1 windows, window
+ * i covers [i*s, min(i*s + p, S)) — the last one may be shorter, S <= p gives one window, and every voxel lies in at least
+ * one window.  nW = nd*nh*nw, window w = (id*nh + ih)*nw + iw.
+ * Regions.  Instead of a grid, `labels` is an int32 volume [D][H][W] with labels 0..R: 0 is background and never occluded,
+ * job r-1 occludes the voxels with label r (nW = R); a label outside 0..R occludes nothing and maps to 0.
+ * Jobs.  Job j = b*nW + w is sample b with window / region w replaced by fill[b] (one float per sample).
+ * Drop.  drops[b][w] = score(unoccluded) - score(job), computed by the caller.
+ * Voxel map.  Grid: vmap[b][z][y][x] = the mean of drops[b][w] over the windows that contain the voxel — the sum in
+ * ascending w in fp32, then ONE division by the count.  Regions: vmap = drops[b][label - 1], 0 elsewhere.
+ *
+ * tmf_occlusion_windows: nW of a geometry, or the negative TMF_E_* the other entries return for it.
+ * tmf_occlude_windows / tmf_occlude_labels: out[k] ([K][D][H][W]) = vol[(j0+k) / nW] with window / region (j0+k) % nW set to
+ *   fill[(j0+k) / nW]; a chunk may straddle samples.  ONE launch, a pure copy: the bits of clone() plus slice assignment.
+ * tmf_occlusion_volume / tmf_occlusion_volume_labels: drops [B][nW] -> vmap [B][D][H][W], ONE launch, a gather (one output
+ *   voxel per lane element, no atomics): two calls give the same bits.
+ * 16 bytes per lane where D*H*W % 4 == 0 and vol, out, vmap (and labels) are 16-byte aligned, one element per lane
+ * otherwise; every pointer 4-byte aligned (TMF_E_ALIGN).  Limits (TMF_E_SHAPE / TMF_E_ARG, nothing launched): extents >= 1
+ * with D*H*W < 2^31 (element offsets inside a volume are 32-bit, between volumes 64-bit); patch >= 1, 1 <= stride <= patch
+ * per axis; R >= 1; B >= 1 with B*nW < 2^31; j0 >= 0, 1 <= K <= 65536, j0 + K <= B*nW; B <= 65536 for the voxel maps. */
+int    tmf_occlusion_windows(int D, int H, int W, int pd, int ph, int pw, int sd, int sh, int sw);
+int    tmf_occlude_windows(const float* vol, const float* fill, float* out, int B, int D, int H, int W, int pd, int ph, int pw,
+                           int sd, int sh, int sw, int j0, int K, void* stream);
+int    tmf_occlude_labels(const float* vol, const int* labels, const float* fill, float* out, int B, int D, int H, int W, int R,
+                          int j0, int K, void* stream);
+int    tmf_occlusion_volume(const float* drops, float* vmap, int B, int D, int H, int W, int pd, int ph, int pw, int sd, int sh,
+                            int sw, void* stream);
+int    tmf_occlusion_volume_labels(const float* drops, const int* labels, float* vmap, int B, int D, int H, int W, int R,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

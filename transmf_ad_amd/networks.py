@@ -72,6 +72,7 @@ class sNet(nn.Module):
         self.tmf_alone = False              # True: nothing runs beside this encoder (model_single): tmf_snet_desc.flags = TMF_SNET_ALONE
         self.tmf_algo = None                # None: the process options; a dict: this encoder's own kernels (set_algorithm)
         self.tmf_tap = None                 # None, or a callable (block index, channels-last block output): see TAP_LAYERS
+        self.tmf_replay = None              # None, or a channels-last (K, d, h, w, C) tensor returned in place of a forward: below
 
     # tmf_tap: the encoder's feature maps for whoever needs them (gradcam.py).  The Sequentials below are parameter holders —
     # forward hooks on them never fire, and the one-call paths keep the activations inside a library workspace — so with a
@@ -81,6 +82,19 @@ class sNet(nn.Module):
     # tensor of "conv3" / "conv3.2" (there as (B, C, d, h, w)).  The blocks ahead of a pool (0, 2, 4, 6) are fused with it and
     # never store their pre-pool activations, so `conv1[2]`, `conv2[5]`, `conv3[5]` and `conv4[5]` are not offered.
     TAP_LAYERS = {"conv1": 0, "conv2.2": 1, "conv2": 2, "conv3.2": 3, "conv3": 4, "conv4.2": 5, "conv4": 6}
+
+    # tmf_replay: an encoder whose input did not change need not run again (occlusion.py: blanking a region of the MRI leaves
+    # the PET encoder's output where it was, for every window).  With a channels-last tensor (K, d, h, w, C) here,
+    # forward_channels_last(vol) launches nothing and does not read vol: it checks K == vol.shape[0], (d, h, w) ==
+    # (D // 16, H // 16, W // 16) and C == the encoder's width (ValueError otherwise) and returns the tensor itself.  Whoever
+    # sets it owns its rows (the baseline output indexed to the samples of the batch) and takes it off again.
+    def _replayed(self, replay, vol):
+        B, _, D, H, W = vol.shape
+        want = (B, D // 16, H // 16, W // 16, self.conv4[3].out_channels)
+        if not torch.is_tensor(replay) or tuple(replay.shape) != want:
+            got = tuple(replay.shape) if torch.is_tensor(replay) else type(replay).__name__
+            raise ValueError(f"sNet.tmf_replay is {got}, the volumes {tuple(vol.shape)} give {want}")
+        return replay
 
     def set_precision(self, conv="fp32", storage="fp32"):
         """Precision of THIS encoder's convolution products ("fp32" | "bf16" | "fp32x") and of the activations between its
@@ -100,6 +114,9 @@ class sNet(nn.Module):
     def forward_channels_last(self, vol):
         if vol.dim() != 5 or vol.shape[1] != 1:
             raise ValueError(f"sNet expects (B, 1, D, H, W), got {tuple(vol.shape)}")
+        replay = getattr(self, "tmf_replay", None)
+        if replay is not None:
+            return self._replayed(replay, vol)
         B, _, D, H, W = vol.shape
         x = vol.reshape(B, D, H, W, 1)          # C == 1: NCDHW and NDHWC are the same bytes
         if self.training:                       # all seven counters in one multi-tensor launch

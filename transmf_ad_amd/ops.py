@@ -1338,6 +1338,143 @@ def cam(act, grad, method="gradcam", relu=True, normalize=True):
     return out, weights, peak
 
 
+# --------------------------------------------------------------------------------------
+# occlusion sensitivity (csrc/occlusion.hip; include/tmf_hip.h states the window grid, the jobs and the voxel map)
+# --------------------------------------------------------------------------------------
+
+def occlusion_grid(size, patch, stride):
+    """(nd, nh, nw): per axis n = ceil(max(S - p, 0) / s) + 1 windows; ValueError unless 1 <= s <= p and S >= 1."""
+    size, patch, stride = tuple(size), tuple(patch), tuple(stride)
+    if not (len(size) == len(patch) == len(stride) == 3):
+        raise ValueError(f"size, patch and stride are three numbers each, got {size}, {patch}, {stride}")
+    for S, p, s in zip(size, patch, stride):
+        if any(not isinstance(v, int) or isinstance(v, bool) for v in (S, p, s)) or S < 1 or p < 1:
+            raise ValueError(f"extents and patches are positive integers, got size {size}, patch {patch}, stride {stride}")
+        if not 1 <= s <= p:
+            raise ValueError(f"stride {stride} must lie in 1..patch {patch} on every axis: voxels would lie in no window")
+    return tuple(-(-max(S - p, 0) // s) + 1 for S, p, s in zip(size, patch, stride))
+
+
+def occlusion_window(size, patch, stride, w):
+    """The three slices of window w = (id*nh + ih)*nw + iw: [i*s, min(i*s + p, S)) per axis."""
+    _nd, nh, nw = occlusion_grid(size, patch, stride)
+    idx = (w // (nh * nw), w // nw % nh, w % nw)
+    return tuple(slice(i * s, min(i * s + p, S)) for i, S, p, s in zip(idx, size, patch, stride))
+
+
+def occlusion_ok(*tensors):
+    """The occlusion kernels take these: contiguous float32 (int32 for labels) tensors on one HIP device, none empty."""
+    dev = tensors[0].device
+    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32) and t.is_contiguous() and t.numel() > 0
+               for t in tensors)
+
+
+def _occlusion_out(vol, K, out):
+    shape = (K,) + tuple(vol.shape[1:])
+    if out is None:
+        return torch.empty(shape, device=vol.device, dtype=vol.dtype)
+    if tuple(out.shape) != shape or out.dtype != vol.dtype or out.device != vol.device:
+        raise ValueError(f"out must be {shape} {vol.dtype} on {vol.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    return out
+
+
+def _occlusion_jobs(B, nW, j0, K):
+    if not (K >= 1 and j0 >= 0 and j0 + K <= B * nW):
+        raise ValueError(f"jobs {j0} .. {j0 + K - 1} of {B * nW}")
+
+
+def occlude_windows(vol, fill, patch, stride, j0, K, out=None):
+    """out[k] = vol[(j0+k) // nW] with window (j0+k) % nW of its last three axes set to fill[(j0+k) // nW]: vol (B, ..., D, H, W),
+    fill (B,) -> (K, ..., D, H, W), the bits of clone() plus slice assignment.  Contiguous float32 HIP tensors: ONE launch
+    (tmf_occlude_windows); anything else: those torch ops.  out: a buffer to write into (contiguous for the kernel)."""
+    B, size = vol.shape[0], tuple(vol.shape[-3:])
+    grid = occlusion_grid(size, patch, stride)
+    nW = grid[0] * grid[1] * grid[2]
+    _occlusion_jobs(B, nW, j0, K)
+    out = _occlusion_out(vol, K, out)
+    if tuple(fill.shape) != (B,):
+        raise ValueError(f"fill must be ({B},), got {tuple(fill.shape)}")
+    if occlusion_ok(vol, fill, out) and vol.dtype == _f32 and fill.dtype == _f32 \
+            and vol.numel() == B * size[0] * size[1] * size[2]:             # one channel: (B, 1, D, H, W) or (B, D, H, W)
+        _chk(vol, "vol")
+        _lib.call("tmf_occlude_windows", vol.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *size, *patch, *stride, j0, K,
+                  _stream())
+        return out
+    jobs = torch.arange(j0, j0 + K, device=vol.device)
+    out.copy_(vol.index_select(0, jobs // nW))
+    for k in range(K):
+        b, w = divmod(j0 + k, nW)
+        out[k][(..., *occlusion_window(size, patch, stride, w))] = fill[b]
+    return out
+
+
+def occlude_labels(vol, labels, fill, R, j0, K, out=None):
+    """occlude_windows with regions: job (j0+k) = b*R + (r-1) sets the voxels of sample b whose label (labels (D, H, W),
+    integers) is r to fill[b]; label 0 and labels outside 0..R occlude nothing.  Kernel: tmf_occlude_labels (int32 labels)."""
+    B, size = vol.shape[0], tuple(vol.shape[-3:])
+    if tuple(labels.shape) != size or labels.dtype.is_floating_point or R < 1:
+        raise ValueError(f"labels must be integers of shape {size} and R >= 1, got {tuple(labels.shape)} {labels.dtype}, R = {R}")
+    _occlusion_jobs(B, R, j0, K)
+    out = _occlusion_out(vol, K, out)
+    if tuple(fill.shape) != (B,):
+        raise ValueError(f"fill must be ({B},), got {tuple(fill.shape)}")
+    if occlusion_ok(vol, fill, out, labels) and vol.dtype == _f32 and fill.dtype == _f32 and labels.dtype == torch.int32 \
+            and vol.numel() == B * labels.numel():
+        _chk(vol, "vol")
+        _lib.call("tmf_occlude_labels", vol.data_ptr(), labels.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *size, R, j0, K,
+                  _stream())
+        return out
+    for k in range(K):
+        b, r = divmod(j0 + k, R)
+        out[k] = torch.where(labels.to(vol.device) == r + 1, fill[b], vol[b])
+    return out
+
+
+def occlusion_volume_torch(drops, size, patch=None, stride=None, labels=None):
+    """occlusion_volume in plain torch ops on whatever device and dtype the drops have: a scatter-add per window in ascending w
+    and one division by the count; labels: a lookup."""
+    size = tuple(size)
+    B, nW = drops.shape
+    if labels is not None:
+        lab = labels.to(drops.device).long()
+        picked = drops[:, (lab - 1).clamp(0, nW - 1).reshape(-1)].view((B,) + size)
+        return torch.where((lab >= 1) & (lab <= nW), picked, torch.zeros((), device=drops.device, dtype=drops.dtype))
+    acc = torch.zeros((B,) + size, device=drops.device, dtype=drops.dtype)
+    cnt = torch.zeros(size, device=drops.device, dtype=drops.dtype)
+    for w in range(nW):
+        win = occlusion_window(size, patch, stride, w)
+        acc[(slice(None), *win)] += drops[:, w].view(B, 1, 1, 1)
+        cnt[win] += 1
+    return acc / cnt
+
+
+def occlusion_volume(drops, size, patch=None, stride=None, labels=None):
+    """The drops back on the voxel grid -> (B, D, H, W).  Grid (drops (B, nW), patch, stride): the mean of drops[b, w] over the
+    windows that contain the voxel, summed in ascending w, one division by the count.  labels (D, H, W) (drops (B, R)):
+    drops[b, label - 1], 0 on background and on labels outside 1..R.  Contiguous float32 HIP drops (int32 labels): ONE launch
+    (tmf_occlusion_volume / tmf_occlusion_volume_labels), a gather without atomics; anything else: torch ops in the same order."""
+    size = tuple(size)
+    B, nW = drops.shape
+    if labels is None:
+        grid = occlusion_grid(size, patch, stride)
+        if nW != grid[0] * grid[1] * grid[2]:
+            raise ValueError(f"drops {tuple(drops.shape)} do not belong to the {grid} windows of {size}")
+        if occlusion_ok(drops) and drops.dtype == _f32:
+            _chk(drops, "drops")
+            vmap = torch.empty((B,) + size, device=drops.device, dtype=_f32)
+            _lib.call("tmf_occlusion_volume", drops.data_ptr(), vmap.data_ptr(), B, *size, *patch, *stride, _stream())
+            return vmap
+        return occlusion_volume_torch(drops, size, patch, stride)
+    if tuple(labels.shape) != size or labels.dtype.is_floating_point:
+        raise ValueError(f"labels must be integers of shape {size}, got {tuple(labels.shape)} {labels.dtype}")
+    if occlusion_ok(drops, labels) and drops.dtype == _f32 and labels.dtype == torch.int32:
+        _chk(drops, "drops")
+        vmap = torch.empty((B,) + size, device=drops.device, dtype=_f32)
+        _lib.call("tmf_occlusion_volume_labels", drops.data_ptr(), labels.data_ptr(), vmap.data_ptr(), B, *size, nW, _stream())
+        return vmap
+    return occlusion_volume_torch(drops, size, labels=labels)
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
