@@ -992,6 +992,41 @@ int    tmf_occlusion_volume(const float* drops, float* vmap, int B, int D, int H
 int    tmf_occlusion_volume_labels(const float* drops, const int* labels, float* vmap, int B, int D, int H, int W, int R,
                                    void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Deletion / insertion curves (csrc/faithfulness.hip; Petsiuk et al., RISE, 2018): rank the voxels of a volume by an
+ * attribution, blank (deletion) or reveal (insertion) the top n_1 <= n_2 <= ... <= n_S of them, run the network each time.
+ * The reference has no such function; these entries replace the loop its user writes around the deployed model:
+ * `srt = attr.sort(descending=True); for k: x = torch.where(attr >= srt[n_k - 1], fill, vol); score[k] = model(x)`.
+ *
+ * Ordering.  Voxels are ordered by a = attr + 0.0f (-0.0 ranks with +0.0), compared as floats; infinities are ordinary
+ * values.  NaN is not supported: the values written are then unspecified, but nothing faults or is written out of bounds.
+ * Ties go together, there is no tie-break by index: a step removes every voxel at or above its threshold.
+ *
+ * tmf_rank_thresholds: attr [B][V], counts[S] (HOST memory, read during the call; non-decreasing, each in 1..V, repeats
+ *   allowed) -> thr [B][S] float, thr[b][k] = the counts[k]-th largest a of row b, one of the row's values bit for bit; and
+ *   removed [B][S] int32 = the number of voxels of row b with a >= thr[b][k] (>= counts[k], equal where the values are
+ *   distinct).  Both exact: a multi-quantile radix select on the order-preserving uint32 image of a, digits of 11, 11 and
+ *   10 bits, integer counting only — two calls give the same bits; no sort.  Seven stream operations whatever B and V (one
+ *   hipMemsetAsync of the workspace — the ENTRY zeroes it, the caller need not — and six launches), no host
+ *   synchronisation, no device-to-host copy.  workspace: tmf_rank_workspace_bytes(B, V, S) bytes (0 for arguments the
+ *   entry refuses), 16-byte aligned.
+ * tmf_mask_by_rank: job j = b*(S+1) + s, s in 0..S; m(v) = false for s == 0, else a[b][v] >= thr[b][s-1].  out[k]
+ *   ([K][V], job j0 + k) = m ? f : vol[b] (mode TMF_RANK_DELETION) or m ? vol[b] : f (TMF_RANK_INSERTION), with
+ *   f = base[b][v] where `base` ([B][V], e.g. a blurred copy) is non-NULL, else fill[b] (one float per sample; `fill` may be
+ *   NULL where base is given).  A chunk may straddle samples.  ONE launch, a pure select: the bits of torch.where.
+ * 16 bytes per lane where V % 4 == 0 and attr (and vol, base, out) are 16-byte aligned, one element per lane otherwise;
+ * every pointer 4-byte aligned, the workspace 16-byte (TMF_E_ALIGN).  Limits (TMF_E_SHAPE / TMF_E_ARG / TMF_E_WORKSPACE, nothing launched):
+ * B >= 1 (<= 65536 for the thresholds), 1 <= V < 2^31, 1 <= S <= TMF_RANK_MAX_STEPS, B*(S+1) < 2^31; j0 >= 0,
+ * 1 <= K <= 65536, j0 + K <= B*(S+1). */
+#define TMF_RANK_MAX_STEPS 64
+#define TMF_RANK_DELETION  0
+#define TMF_RANK_INSERTION 1
+size_t tmf_rank_workspace_bytes(int B, long V, int S);
+int    tmf_rank_thresholds(const float* attr, const int* counts, float* thr, int* removed, void* workspace,
+                           size_t workspace_bytes, int B, long V, int S, void* stream);
+int    tmf_mask_by_rank(const float* vol, const float* attr, const float* thr, const float* fill, const float* base, float* out,
+                        int B, long V, int S, int mode, int j0, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

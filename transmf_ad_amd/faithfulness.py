@@ -1,0 +1,205 @@
+"""Which explanation to believe for a scan: deletion / insertion curves (Petsiuk et al., RISE, 2018), the quantitative check on
+input_gradients, attention_maps, grad_cam and occlusion_sensitivity.
+
+    from transmf_ad_amd import faithfulness_curve
+    fc = faithfulness_curve(model.eval(), mri, pet, attribution=a, volume=0, steps=20, mode="deletion")
+    fc.scores       # (B, steps+1): the class score with the top 0, n_1, .. n_steps voxels of the attribution blanked
+    fc.auc          # (B,): the area under it on the nominal grid k / steps; low is good for deletion, high for insertion
+    fc.removed      # (B, steps+1) int32: the voxels really blanked (revealed) at each step, column 0 is 0
+    fc.thresholds   # (B, steps)
+    fc.logits, fc.target, fc.base_score, fc.steps, fc.mode, fc.volume
+
+Semantics (include/tmf_hip.h states the same for the kernels):
+  Attribution.  `attribution` (B, D, H, W) or (B, 1, D, H, W) holds one value per voxel of volume argument `volume` (0 = the
+    first): |input gradient|, a Grad-CAM map the caller upsampled, occ.volume(i), ...  Voxels are ordered by a = attribution
+    + 0.0 (-0.0 ranks with +0.0), compared as floats in the attribution's own dtype; infinities are ordinary values.  NaN
+    raises ValueError: this is ONE host read (a device synchronisation) before the pass.
+  Steps.  n_k = ceil(k*V / steps), k = 1..steps (ops.rank_counts); thresholds[b, k-1] = the n_k-th largest a of sample b.
+    Step k masks every voxel with a >= that threshold: ties go together, there is no tie-break by index, so
+    removed[b, k] >= n_k with equality where the values are distinct, and equal steps repeat (V < steps, plateaus).
+  Jobs.  Job j = b*(steps+1) + s, s = 0..steps; s = 0 masks nothing and runs like every other job.  mode "deletion": the
+    masked voxels are replaced by f, the others keep the volume.  mode "insertion": the masked voxels show the volume, the
+    others f.  f = baseline[b, voxel] where `baseline` (a tensor of the volume's shape, e.g. a blurred copy) is given, else
+    fill[b]: a float (default 0.0), "mean" (the sample's mean) or a tensor (B,), as in occlusion_sensitivity.
+  Score.  "prob" (default): the softmax probability of class target_b; "logit": logits[b, target_b].  target as
+    saliency.input_gradients (None: the argmax of the UNMASKED logits, resolved once).  base_score is that forward's score.
+  AUC.  auc = (s_0/2 + s_1 + .. + s_{S-1} + s_S/2) / S by torch ops; `removed` lets a caller integrate over the true
+    fractions removed / V where ties make the steps uneven.
+  Model mode.  The model must be in eval mode (ValueError otherwise: train-mode BatchNorm would mix the jobs of a chunk).
+    Everything runs under torch.no_grad(); the caller's tensors, the parameters' .grad, the buffers and torch's generator stay
+    untouched.
+
+The thresholds come from ONE call (ops.rank_thresholds: tmf_rank_thresholds, csrc/faithfulness.hip, a radix select without a
+sort).  The jobs are walked in chunks of `chunk`: ONE launch (ops.mask_by_rank: tmf_mask_by_rank) writes the chunk's masked
+volumes into a buffer allocated once, one model(...) call runs, the scores come from the (K, classes) logits by torch ops.
+
+reuse=True is occlusion's machinery as it stands (occlusion._baseline, occlusion._Replay): every networks.sNet of a package
+model that ran once in the unmasked forward, on a volume argument other than `volume`, keeps its output and replays it
+through sNet.tmf_replay for the pass, taken off again also when the model raises.
+
+faithfulness_curve_torch is the same function on sort(descending=True), a gather, >= and torch.where, on any device and
+dtype and any nn.Module (the reference's classes on the CPU in float or double); tmf_replay is not used there."""
+import contextlib
+
+import torch
+from torch import nn
+
+from . import ops
+from .occlusion import SCORES, _Replay, _baseline, _score
+from .saliency import _check, _logits, _resolve_target
+
+__all__ = ["faithfulness_curve", "faithfulness_curve_torch", "Faithfulness", "MODES"]
+
+MODES = tuple(ops.RANK_MODES)
+
+
+class Faithfulness:
+    """scores (B, steps+1), auc (B,), removed (B, steps+1) int32, thresholds (B, steps); logits (B, classes): the unmasked
+    forward; target (B,): the class scored; base_score (B,); steps, mode, volume."""
+
+    def __init__(self, scores, auc, removed, thresholds, logits, target, base_score, steps, mode, volume):
+        self.scores, self.auc, self.removed, self.thresholds = scores, auc, removed, thresholds
+        self.logits, self.target, self.base_score = logits, target, base_score
+        self.steps, self.mode, self.volume = steps, mode, volume
+
+
+def _fill(fill, v, B):
+    msg = f"fill must be a float, \"mean\" or a tensor ({B},), got {fill!r}"
+    if isinstance(fill, str):
+        if fill != "mean":
+            raise ValueError(msg)
+        return v.reshape(B, -1).mean(1)
+    if torch.is_tensor(fill):
+        if tuple(fill.shape) != (B,):
+            raise ValueError(f"a fill tensor must be ({B},), got {tuple(fill.shape)}")
+        return fill.detach().to(device=v.device, dtype=v.dtype).contiguous()
+    if isinstance(fill, (int, float)) and not isinstance(fill, bool):
+        return torch.full((B,), float(fill), device=v.device, dtype=v.dtype)
+    raise ValueError(msg)
+
+
+def _run(model, volumes, attribution, volume, steps, mode, fill, baseline, score, target, output, chunk, reuse, torch_only):
+    _check(volumes)
+    if not isinstance(model, nn.Module):
+        raise TypeError(f"faithfulness_curve: {type(model).__name__} is not an nn.Module")
+    if any(m.training for m in model.modules()):
+        raise ValueError("faithfulness_curve explains the deployed network: call model.eval() first (train-mode BatchNorm "
+                         "would mix the jobs of a chunk)")
+    if score not in SCORES:
+        raise ValueError(f"score must be one of {SCORES}, got {score!r}")
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    if not isinstance(steps, int) or isinstance(steps, bool) or not 1 <= steps <= 64:
+        raise ValueError(f"steps must be an integer in 1..64, got {steps!r}")
+    if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, got {chunk!r}")
+    vols = [v.detach() for v in volumes]
+    if not isinstance(volume, int) or isinstance(volume, bool) or not 0 <= volume < len(vols):
+        raise ValueError(f"volume must name one of the {len(vols)} volume arguments, got {volume!r}")
+    B = vols[0].shape[0]
+    if any(v.dim() < 4 or v.shape[0] != B for v in vols):
+        raise ValueError("volumes must be (B, ..., D, H, W) with one batch size")
+    v = vols[volume]
+    size = tuple(int(s) for s in v.shape[-3:])
+    V = size[0] * size[1] * size[2]
+    if B < 1 or V < 1 or v.numel() != B * V:
+        raise ValueError("the masked volume must be a one-channel volume (B, 1, D, H, W) with voxels")
+    if not torch.is_tensor(attribution) or not attribution.dtype.is_floating_point \
+            or tuple(attribution.shape) not in ((B,) + size, (B, 1) + size):
+        raise ValueError(f"attribution must be a floating-point tensor ({B}, {size[0]}, {size[1]}, {size[2]}) or with a channel "
+                         f"axis of 1, got {tuple(attribution.shape) if torch.is_tensor(attribution) else attribution!r}")
+    attr = attribution.detach().to(v.device).contiguous()
+    if bool(torch.isnan(attr).any()):                                   # the one host read
+        raise ValueError("attribution holds NaN: voxels cannot be ranked")
+    base_vol = None
+    if baseline is not None:
+        if not torch.is_tensor(baseline) or tuple(baseline.shape) != tuple(v.shape):
+            raise ValueError(f"baseline must be a tensor of the volume's shape {tuple(v.shape)}")
+        base_vol = baseline.detach().to(device=v.device, dtype=v.dtype).contiguous()
+    fills = _fill(fill, v, B)
+    counts = ops.rank_counts(V, steps)
+    S, nJ = steps, B * (steps + 1)
+
+    def thresholds():
+        if not torch_only:
+            return ops.rank_thresholds(attr, counts)
+        a = attr.reshape(B, V) + 0.0
+        srt = a.sort(1, descending=True).values
+        thr = srt.gather(1, torch.tensor(counts, device=a.device).view(1, S).expand(B, S) - 1)
+        return thr, torch.stack([(a >= thr[:, k:k + 1]).sum(1) for k in range(S)], 1).to(torch.int32)
+
+    def masked(thr, j0, K, out):
+        if not torch_only:
+            return ops.mask_by_rank(v, attr, thr, fills, mode, j0, K, base=base_vol, out=out)
+        a = attr.reshape(v.shape) + 0.0
+        xs = []
+        for j in range(j0, j0 + K):                                     # torch.where, as a user writes it
+            b, s = divmod(j, S + 1)
+            m = a[b] >= thr[b, s - 1] if s else torch.zeros_like(a[b], dtype=torch.bool)
+            f = base_vol[b] if base_vol is not None else fills[b]
+            xs.append(torch.where(m, f, v[b]) if mode == "deletion" else torch.where(m, v[b], f))
+        return torch.stack(xs)
+
+    # the library launches on the CURRENT device's current stream: make the volumes' device current for the duration
+    guard = torch.cuda.device(vols[0].device) if vols[0].is_cuda else contextlib.nullcontext()
+    with torch.no_grad(), guard:
+        logits, encoders = _baseline(model, vols, output, reuse and not torch_only)
+        target = _resolve_target(target, logits)
+        base = _score(logits, target, score)
+        sides = []
+        if logits.is_cuda:
+            # the two-encoder models run one encoder on a side stream: order it ahead of the reads of its kept output
+            from . import mymodel
+            cur = torch.cuda.current_stream(logits.device)
+            sides = mymodel.backward_streams(logits.device)
+            for s in sides:
+                cur.wait_stream(s)
+            for encs in encoders.values():
+                for _enc, out in encs:
+                    out.record_stream(cur)
+        thr, removed = thresholds()
+        kept = [e for i, encs in encoders.items() if i != volume for e in encs]
+        replayed = {i for i in encoders if i != volume}
+        # the chunk buffer of the kernel path, allocated once per pass (the torch ops allocate as they go)
+        tensors = (v, attr, thr) + ((base_vol,) if base_vol is not None else (fills,))
+        buf = torch.empty((min(chunk, nJ),) + tuple(v.shape[1:]), device=v.device, dtype=v.dtype) \
+            if not torch_only and ops.faithfulness_ok(*tensors) else None
+        scores = torch.empty((nJ,), device=logits.device, dtype=logits.dtype)
+        with _Replay(kept) as replay:
+            for j0 in range(0, nJ, chunk):
+                K = min(chunk, nJ - j0)
+                rows = torch.arange(j0, j0 + K, device=logits.device) // (S + 1)
+                batch = []
+                for i, x in enumerate(vols):
+                    if i == volume:
+                        batch.append(masked(thr, j0, K, None if buf is None else buf[:K]))
+                    elif i in replayed:
+                        batch.append(x[:1].expand(K, *x.shape[1:]))        # not read: its encoder replays
+                    else:
+                        batch.append(x.index_select(0, rows.to(x.device)))
+                replay.set(rows)
+                out = _logits(model, batch, output)
+                scores[j0:j0 + K] = _score(out, target.index_select(0, rows), score)
+        if buf is not None:
+            for s in sides:
+                buf.record_stream(s)
+        scores = scores.view(B, S + 1)
+        auc = (scores[:, 0] / 2 + scores[:, 1:S].sum(1) + scores[:, S] / 2) / S
+        removed = torch.cat([torch.zeros((B, 1), device=removed.device, dtype=removed.dtype), removed], 1)
+    return Faithfulness(scores, auc, removed, thr, logits, target, base, S, mode, volume)
+
+
+def faithfulness_curve(model, *vols, attribution, volume=0, steps=20, mode="deletion", fill=0.0, baseline=None, score="prob",
+                       target=None, output=0, chunk=32, reuse=True):
+    """The deletion or insertion curve of `attribution` for volume argument `volume` of `model` (eval mode) -> Faithfulness.
+    See the module docstring for the ordering, steps, jobs, fill / baseline, score, target, chunk and reuse.  ValueError for
+    a model in train mode, steps outside 1..64, a bad mode, score, volume, fill, baseline or attribution shape, and an
+    attribution that holds NaN (one host read before the pass)."""
+    return _run(model, vols, attribution, volume, steps, mode, fill, baseline, score, target, output, chunk, bool(reuse), False)
+
+
+def faithfulness_curve_torch(model, *vols, attribution, volume=0, steps=20, mode="deletion", fill=0.0, baseline=None,
+                             score="prob", target=None, output=0, chunk=32, reuse=False):
+    """faithfulness_curve on sort(descending=True), a gather, >= and torch.where: any device, dtype and nn.Module.  `reuse` is
+    accepted and ignored: tmf_replay is not used here."""
+    return _run(model, vols, attribution, volume, steps, mode, fill, baseline, score, target, output, chunk, False, True)

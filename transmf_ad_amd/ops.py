@@ -6,6 +6,7 @@ fp32, contiguous, on a HIP device; activations are channels-last (B, D, H, W, C)
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -1473,6 +1474,97 @@ def occlusion_volume(drops, size, patch=None, stride=None, labels=None):
         _lib.call("tmf_occlusion_volume_labels", drops.data_ptr(), labels.data_ptr(), vmap.data_ptr(), B, *size, nW, _stream())
         return vmap
     return occlusion_volume_torch(drops, size, labels=labels)
+
+
+# --------------------------------------------------------------------------------------
+# deletion / insertion curves (csrc/faithfulness.hip; include/tmf_hip.h states the ordering, the thresholds and the jobs)
+# --------------------------------------------------------------------------------------
+
+RANK_MODES = {"deletion": _lib.RANK_DELETION, "insertion": _lib.RANK_INSERTION}
+
+
+def rank_counts(V, steps):
+    """[n_1 .. n_steps], n_k = ceil(k*V / steps): the number of voxels step k removes at least.  Non-decreasing, each in
+    1..V, n_steps = V; repeated where V < steps."""
+    if any(not isinstance(v, int) or isinstance(v, bool) for v in (V, steps)) or V < 1 or not 1 <= steps <= _lib.RANK_MAX_STEPS:
+        raise ValueError(f"V must be a positive integer and steps one in 1..{_lib.RANK_MAX_STEPS}, got V = {V!r}, steps = {steps!r}")
+    return [-(-k * V // steps) for k in range(1, steps + 1)]
+
+
+def faithfulness_ok(*tensors):
+    """The kernels of csrc/faithfulness.hip take these: contiguous float32 tensors on one HIP device, none empty."""
+    dev = tensors[0].device
+    return all(t.is_cuda and t.device == dev and t.dtype == _f32 and t.is_contiguous() and t.numel() > 0 for t in tensors)
+
+
+def _rank_counts_checked(V, counts):
+    counts = [int(c) for c in counts]
+    S = len(counts)
+    if not 1 <= S <= _lib.RANK_MAX_STEPS or counts[0] < 1 or counts[-1] > V or any(a > b for a, b in zip(counts, counts[1:])):
+        raise ValueError(f"counts must be 1..{_lib.RANK_MAX_STEPS} non-decreasing numbers in 1..{V}, got {counts}")
+    return counts
+
+
+def rank_thresholds(attr, counts):
+    """attr (B, ...) with V elements per sample, counts [S] (rank_counts) -> (thr (B, S) of attr's dtype, removed (B, S) int32):
+    thr[b, k] = the counts[k]-th largest a = attr + 0.0 of sample b, removed[b, k] = the number of its voxels with a >= thr[b, k]
+    (ties go together).  Contiguous float32 HIP tensors: a radix select without a sort (tmf_rank_thresholds); anything else:
+    sort(descending=True), a gather and >=."""
+    B = attr.shape[0]
+    a = attr.reshape(B, -1)
+    V = a.shape[1]
+    if B < 1 or V < 1:
+        raise ValueError(f"attr must hold samples with voxels, got {tuple(attr.shape)}")
+    counts = _rank_counts_checked(V, counts)
+    S = len(counts)
+    if faithfulness_ok(attr):
+        _chk(attr, "attr")
+        thr = torch.empty((B, S), device=attr.device, dtype=_f32)
+        removed = torch.empty((B, S), device=attr.device, dtype=torch.int32)
+        nws = _lib.query("tmf_rank_workspace_bytes", B, V, S)
+        ws = torch.empty((nws,), device=attr.device, dtype=torch.uint8)        # the entry zeroes it
+        _lib.call("tmf_rank_thresholds", attr.data_ptr(), (ctypes.c_int * S)(*counts), thr.data_ptr(), removed.data_ptr(),
+                  ws.data_ptr(), nws, B, V, S, _stream())
+        return thr, removed
+    a = a + 0.0
+    srt = a.sort(1, descending=True).values
+    thr = srt.gather(1, torch.tensor(counts, device=a.device).view(1, S).expand(B, S) - 1)
+    removed = torch.stack([(a >= thr[:, k:k + 1]).sum(1) for k in range(S)], 1).to(torch.int32)
+    return thr, removed
+
+
+def mask_by_rank(vol, attr, thr, fill, mode, j0, K, base=None, out=None):
+    """Job j0 + k = b*(S+1) + s, s in 0..S: m = (s > 0) & (attr[b] + 0.0 >= thr[b, s-1]); out[k] = where(m, f, vol[b]) for mode
+    "deletion", where(m, vol[b], f) for "insertion", f = base[b] (a tensor of vol's shape) where given, else fill[b] (fill (B,)).
+    vol, attr (B, ...) with the same number of elements, thr (B, S) -> (K, ...) of vol's shape.  Contiguous float32 HIP
+    tensors: ONE launch (tmf_mask_by_rank); anything else: torch.where.  out: a buffer to write into."""
+    if mode not in RANK_MODES:
+        raise ValueError(f"mode must be one of {tuple(RANK_MODES)}, got {mode!r}")
+    B = vol.shape[0]
+    if thr.dim() != 2 or thr.shape[0] != B or not 1 <= thr.shape[1] <= _lib.RANK_MAX_STEPS:
+        raise ValueError(f"thr must be ({B}, S) with S in 1..{_lib.RANK_MAX_STEPS}, got {tuple(thr.shape)}")
+    S = thr.shape[1]
+    if attr.shape[0] != B or attr.numel() != vol.numel():
+        raise ValueError(f"attr {tuple(attr.shape)} does not hold one value per voxel of vol {tuple(vol.shape)}")
+    if base is not None and tuple(base.shape) != tuple(vol.shape):
+        raise ValueError(f"base must have vol's shape {tuple(vol.shape)}, got {tuple(base.shape)}")
+    if base is None and (fill is None or tuple(fill.shape) != (B,)):
+        raise ValueError(f"fill must be ({B},), got {None if fill is None else tuple(fill.shape)}")
+    _occlusion_jobs(B, S + 1, j0, K)
+    out = _occlusion_out(vol, K, out)
+    f = base if base is not None else fill
+    if faithfulness_ok(vol, attr, thr, f, out):
+        _chk(vol, "vol")
+        _lib.call("tmf_mask_by_rank", vol.data_ptr(), attr.data_ptr(), thr.data_ptr(), _ptr(None if base is not None else fill),
+                  _ptr(base), out.data_ptr(), B, vol.numel() // B, S, RANK_MODES[mode], j0, K, _stream())
+        return out
+    a = attr.reshape(vol.shape) + 0.0
+    for k in range(K):
+        b, s = divmod(j0 + k, S + 1)
+        m = a[b] >= thr[b, s - 1] if s else torch.zeros_like(a[b], dtype=torch.bool)
+        g = base[b] if base is not None else fill[b].to(vol.dtype)
+        out[k] = torch.where(m, g, vol[b]) if mode == "deletion" else torch.where(m, vol[b], g)
+    return out
 
 
 class FusionTrain(torch.autograd.Function):
