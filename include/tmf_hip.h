@@ -184,6 +184,14 @@ int    tmf_conv3d_wino_bricks(int B, int D, int H, int W);            /* bricks 
 int    tmf_conv3d_wino_bricks2(int B, int D, int H, int W, int cin, int cout);   /* ... of a launch with these channel counts: where the split
                                                                          kernel can take it, the one-sample bricks are kept unless the folded
                                                                          geometry saves more than 15 % of them (round 6) */
+int    tmf_conv3d_wino_grid(int B, int D, int H, int W, int cin, int cout);      /* workgroups of that launch's first window (persistent
+                                                                         kernels: min(items, CUs), evened to the rounds it needs);
+                                                                         statistic rows at and past it are zeros; 0 with "wino_p" 0 */
+int    tmf_xcd_slot(int block, int grid);                             /* the placement rule of the persistent Winograd kernels: the
+                                                                       * window slot (forward / data gradient: items slot + i * grid)
+                                                                       * or split (weight gradient) of workgroup `block`, which runs
+                                                                       * on XCD block % 8 — a permutation of 0 .. grid - 1 that gives
+                                                                       * every XCD one contiguous range, for every grid; -1 outside */
 const char* tmf_conv3d_wino_kernel_name(int B, int D, int H, int W, int stats);        /* the instance a kernel trace shows (as */
 const char* tmf_conv3d_wgrad_wino_kernel_name(int B, int D, int H, int W, int cin, int cout);   /* tmf_conv3d_fwd_kernel_name) */
 long   tmf_conv3d_wgrad_wino_tiles(int B, int D, int H, int W, int cin, int cout);     /* 2x2x2 tiles (padded: 16 per stage) the weight-

@@ -569,9 +569,9 @@ __global__ __launch_bounds__(PN) void conv3d_wino_p_kernel(
     constexpr int OOB = (int)0x80000000u;
 
     // ---- this workgroup's items: item0 + jb + i G; within a window of G consecutive items every XCD (blockIdx % 8) takes a
-    // contiguous range (neighbouring bricks share their halo in that XCD's L2) ----
+    // contiguous range (neighbouring bricks share their halo in that XCD's L2), whatever the grid (xcd_contiguous) ----
     const int G = gridDim.x;
-    const int jb = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int jb = xcd_contiguous(blockIdx.x, G);
     const int my_items = jb < nitems ? (nitems - jb + G - 1) / G : 0;
     if (my_items == 0) return;
     for (int i = tid; i < my_items; i += PN) {
@@ -1267,7 +1267,10 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hsel = lane >> 5;
-    const int split = blockIdx.x, blk = blockIdx.y;
+    // the split this workgroup walks and whose slab it writes: the workgroups of one XCD take NEIGHBOURING splits, i.e. adjacent
+    // stage ranges (the d neighbour of a stage lies two or three splits on), and share the stages' halos in that XCD's L2.  A
+    // split's stages, its slab and the order of the slab reduction are what they were: dw does not change by a bit.
+    const int split = xcd_contiguous(blockIdx.x, gridDim.x), blk = blockIdx.y;
     const int ci0 = (blk / ncob) * 32, co0 = (blk % ncob) * 32;
     const int st0 = split * per_split;
     const int st1 = st0 + per_split < nbricks ? st0 + per_split : nbricks;
@@ -1818,13 +1821,8 @@ int launch_wino_p_g(const char* what, const float* x, const float* u, float* z, 
     const long per_launch = (long)ncu * GM::TAB;            // a workgroup's item table holds TAB entries
     for (long i0 = 0; i0 < nitems; i0 += per_launch) {
         const long n = nitems - i0 < per_launch ? nitems - i0 : per_launch;
-        // as many workgroups as the launch needs for its number of ROUNDS (864 items on 256 CUs are 4 rounds: 216 workgroups
-        // of exactly 4 items take as long as 256 of 3 or 4 and leave 40 CUs to the other encoder's stream)
-        int grid = (int)(n < ncu ? n : ncu);
-        if (tmf_opt(TMF_OPT_WINO_EVEN) && n > ncu) {
-            const long rounds = (n + ncu - 1) / ncu;
-            grid = (int)((n + rounds - 1) / rounds);
-        }
+        // as many workgroups as the launch needs for its number of ROUNDS (tmf_wino_window_grid)
+        const int grid = tmf_wino_window_grid(n, ncu, tmf_opt(TMF_OPT_WINO_EVEN));
         hipLaunchKernelGGL(k, dim3(grid), dim3(PN), PLds<GEOM>::BYTES, stream, x, u, z, stat_partial, B, D, H, W, cin, cout,
                            tilesD, tilesH, tilesW, (int)nbricks, (int)i0, (int)n, scale, shift, slope, pool, ncu, i0 > 0 ? 1 : 0);
         if ((rc = tmf_launch_result(what))) return rc;
@@ -1873,6 +1871,23 @@ extern "C" int tmf_conv3d_wino_bricks2(int B, int D, int H, int W, int cin, int 
         return (int)wino_p_bricks(g, B, D, H, W);
     }
     return B * tmf_cdiv(D, TD) * tmf_cdiv(H, TH) * tmf_cdiv(W, TW);
+}
+// workgroups of the first window of that launch's persistent kernel (the launchers' own rule: tmf_wino_window_grid); 0 with
+// "wino_p" 0, whose kernels are not persistent
+extern "C" int tmf_conv3d_wino_grid(int B, int D, int H, int W, int cin, int cout) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || !tmf_conv3d_wino_ok(cin, cout) || !wino_p_mode()) return 0;
+    const int g = wino_fwd_geom(B, D, H, W, cin, cout), ncu = wino_cu_count();
+    if (tmf_winox_takes(B, D, H, W, cin, cout, g)) return tmf_winox_first_grid(B * tmf_winox_items(D, H, W, nullptr) * (cout / 32), ncu);
+    const bool folded = g && (long)4 * D * H * W * (cin > cout ? cin : cout) < (1L << 29);     // (launch_wino_p)
+    const long nitems = wino_p_bricks(folded ? 1 : 0, B, D, H, W) * (cout / 32);
+    const long per_launch = (long)ncu * (folded ? PGeom<1>::TAB : PGeom<0>::TAB);
+    return tmf_wino_window_grid(nitems < per_launch ? nitems : per_launch, ncu, tmf_opt(TMF_OPT_WINO_EVEN));
+}
+// the placement rule of the persistent Winograd kernels (xcd_contiguous): the window slot jb — items item0 + jb + i * grid; for the
+// weight gradient the split — of workgroup `block` of a grid.  Workgroup b runs on XCD b % 8.
+extern "C" int tmf_xcd_slot(int block, int grid) {
+    if (grid <= 0 || block < 0 || block >= grid) return -1;
+    return xcd_contiguous(block, grid);
 }
 extern "C" int tmf_conv3d_wino_bricks(int B, int D, int H, int W) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;

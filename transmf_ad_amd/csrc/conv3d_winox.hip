@@ -157,9 +157,10 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
     const int nchunk = Cin / XCK;                           // even (Cin % 32 == 0): every item ends on halo pair 1
     constexpr int OOB = (int)0x80000000u;
 
-    // ---- this workgroup's items (the persistent fp32 kernel's order: item0 + jb + i G, XCD-contiguous within a window) ----
+    // ---- this workgroup's items (the persistent fp32 kernel's order: item0 + jb + i G, XCD-contiguous within a window for EVERY
+    // grid: the rounds-sized grids of the 48^3 launches, 247 workgroups, are no multiple of 8) ----
     const int G = gridDim.x;
-    const int jb = (G & 7) == 0 ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int jb = xcd_contiguous(blockIdx.x, G);
     const int my_items = jb < nitems ? (nitems - jb + G - 1) / G : 0;
     if (my_items == 0) return;
     for (int i = tid; i < my_items; i += XN) {
@@ -314,7 +315,9 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
     auto lane_now = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
     // BatchNorm statistic partials (MODE 1): ONE row [2][Cout] per workgroup.  Every reader lane adds its 4 + 4 sums of an item into
     // its OWN cells of `red` (no registers across the main loop); the reduction over the workgroup and the store happen only where
-    // the channel group changes (the items of a workgroup are ordered by group) and at the end.
+    // the channel group changes and at the end.  The channel group is the items' FAST index (X_NGFAST): a workgroup keeps its group
+    // — one flush per launch — where the grid is a multiple of the group count, and changes it with every item where it is not
+    // (a later flush of a group adds into the row: st_seen).
     int st_n0 = -1;
     unsigned st_seen = 0;
     auto stat_zero = [&]() {
@@ -629,6 +632,12 @@ long tmf_winox_items(int D, int H, int W, int* swap) {
     return sw ? t_s : t_n;
 }
 
+// workgroups of the first window of a launch of nitems items (a window holds ncu x TAB items)
+int tmf_winox_first_grid(long nitems, int ncu) {
+    const long per_launch = (long)ncu * TAB;
+    return tmf_wino_window_grid(nitems < per_launch ? nitems : per_launch, ncu, 1);
+}
+
 int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3, float* z, float* stat_partial, int B, int Dt, int Ht,
                      int W, int cin, int cout, int ncu, hipStream_t stream, const float* scale, const float* shift, float slope, int pool) {
     int swap = 0;
@@ -648,11 +657,7 @@ int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3,
         const long per_launch = (long)ncu * TAB;
         for (long i0 = 0; i0 < nitems; i0 += per_launch) {
             const long n = nitems - i0 < per_launch ? nitems - i0 : per_launch;
-            int grid = (int)(n < ncu ? n : ncu);
-            if (n > ncu) {                                  // as many workgroups as the number of rounds needs
-                const long rounds = (n + ncu - 1) / ncu;
-                grid = (int)((n + rounds - 1) / rounds);
-            }
+            const int grid = tmf_wino_window_grid(n, ncu, 1);       // as many workgroups as the number of rounds needs
             hipLaunchKernelGGL(k, dim3(grid), dim3(XN), X_LDS_BYTES, stream, x, u3, z, stat_partial, B, D, H, W, cin, cout,
                                tilesD, tilesH, tilesW, (int)nbricks, (int)i0, (int)n, ncu, i0 > 0 ? 1 : 0, scale, shift, slope, swap);
             if ((rc = tmf_launch_result(what))) return rc;

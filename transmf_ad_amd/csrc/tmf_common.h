@@ -107,6 +107,7 @@ struct TmfAlgoScope {       // options.hip
 };
 int tmf_winox_takes(int B, int D, int H, int W, int cin, int cout, int geom);
 long tmf_winox_items(int D, int H, int W, int* swap);     // items per sample (the better of the two item orientations)
+int tmf_winox_first_grid(long nitems, int ncu);           // workgroups of a launch's first window
 int tmf_winox_launch(const char* what, const float* x, const unsigned short* u3, float* z, float* stat_partial, int B, int D, int H,
                      int W, int cin, int cout, int ncu, hipStream_t stream, const float* scale = nullptr, const float* shift = nullptr,
                      float slope = 0.f, int pool = 0);     // scale != NULL: the eval-mode block (y = LeakyReLU(scale z + shift), pool none | max)
@@ -197,6 +198,16 @@ static inline int tmf_allow_lds(K kernel, size_t bytes, const char* what) {
 static inline int tmf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }     // arena offsets: 256-byte granules
 
+// Workgroups of one window of n items of a persistent Winograd launch on ncu compute units: min(n, ncu), and with `even` as few
+// as the window's number of ROUNDS needs (864 items on 256 CUs are 4 rounds: 216 workgroups of exactly 4 items take as long as
+// 256 of 3 or 4 and leave 40 CUs to the other encoder's stream).  The statistic rows at and past this count are zeros.
+static inline int tmf_wino_window_grid(long n, int ncu, int even) {
+    if (n <= ncu) return (int)n;
+    if (!even) return ncu;
+    const long rounds = (n + ncu - 1) / ncu;
+    return (int)((n + rounds - 1) / rounds);
+}
+
 // Two-stage slab reduction plan: `groups` first-stage groups (1 = single stage straight into `out`).
 static inline int tmf_reduce_groups(int nsplit) {
     if (nsplit <= 64) return 1;
@@ -212,8 +223,10 @@ int tmf_reduce_slabs(const float* partial, int nsplit, long n, float* scratch, f
 #ifdef __HIPCC__
 // MI355X dispatches workgroup b to XCD b % 8 (speed hint only, MI355X_MICROARCH.md).
 // Map the launch index so that each XCD (= one private L2) walks a contiguous range
-// of tiles: neighbouring tiles share their halo in that L2.  Bijective for any n.
-__device__ __forceinline__ int xcd_contiguous(int bid, int n) {
+// of tiles: neighbouring tiles share their halo in that L2.  Bijective for any n: XCD x takes n / 8 indices, the first
+// n % 8 XCDs one more.  The ONE placement rule of the library — the persistent Winograd kernels apply it to their workgroup
+// index (window slot) too; tmf_xcd_slot (conv3d_wino.hip) shows it to host tests.
+__host__ __device__ __forceinline__ int xcd_contiguous(int bid, int n) {
     const int q = n >> 3, r = n & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
