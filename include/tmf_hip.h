@@ -1035,6 +1035,53 @@ int    tmf_rank_thresholds(const float* attr, const int* counts, float* thr, int
 int    tmf_mask_by_rank(const float* vol, const float* attr, const float* thr, const float* fill, const float* base, float* out,
                         int B, long V, int S, int mode, int j0, int K, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Atlas region statistics of attribution maps (csrc/region_stats.hip): which brain regions carry a voxel map.  The reference
+ * has no such function; these entries replace what its user writes with stock ops for every map:
+ * `cnt = bincount(lab); s = bincount(lab, weights=a); s_abs = bincount(lab, weights=a.abs()); s_pos = bincount(lab,
+ * weights=a.clamp(min=0)); mx = full(-inf).scatter_reduce(0, lab, a, "amax"); arg = per region the first index where a == mx`
+ * - five or more passes over the volume with float atomics, whose sums change in their last bits from run to run - and, for
+ * the group table, `for b: n[cls[b]] += 1; sx[cls[b]] += x[b]; sxx[cls[b]] += x[b]**2` in fp64.
+ *
+ * Bins.  a [B][V] float, labels [V] int32 (ONE atlas for all samples: the volumes are registered), R >= 1.  Bin r in 1..R
+ * collects the voxels with label r, bin 0 every other voxel: label 0, negative labels and labels above R (the range is
+ * checked before any index is formed from a label).
+ * Outputs, [B][R+1] but for count: count [R+1] int32 (a property of the atlas alone); sum = the sum of a; abs_sum of |a|;
+ * pos_sum of max(a, 0); max = the largest a + 0.0f of the bin, one of its values bit for bit, -inf for an empty bin; argmax
+ * int32 = the lowest linear voxel index that attains max, -1 for an empty bin.  Each of the five per-sample outputs may be
+ * NULL and is then not written.  count, max and argmax are exact.
+ * Sums.  Integers only, so the bits depend on neither the grid nor the order of arrival, and two calls give the same bits.
+ * With peak_b = max |a[b]|, 2^(e-1) <= peak_b < 2^e and shift = 62 - ceil(log2 V), every |a| is scaled by the power of two
+ * 2^(shift-e) and rounded ONCE to an integer (half away from zero); the positive and the negative voxels of a bin are added
+ * up apart in 64-bit integers (V values below 2^shift stay below 2^62), sum = P - N, abs_sum = P + N, pos_sum = P, each
+ * scaled back in fp64 and rounded once to float.  Against exact arithmetic, with n_r = count[r]:
+ *     |got - exact| <= n_r * peak_b * 2^-shift + 2^-23 * |exact|
+ * (shift >= 31; 42 at 96^3), which lies below n_r * 2^-24 * max(peak_b, sum |a|) + 2^-23 * |exact| for every V.  Sums of
+ * integers below 2^24 are exact.  An all-zero sample gives sums 0, max 0 and argmax = the bin's lowest index.  Non-finite
+ * inputs are not supported: the values written are then unspecified, but nothing faults or is written out of bounds.
+ * Passes.  The map is read TWICE (once for peak_b, once for the bins: the second read of a 96^3 batch comes from the
+ * last-level cache), the labels once per sample, 16 bytes per lane where V % 4 == 0 and `a` and `labels` are 16-byte
+ * aligned, one element per lane otherwise.  Four stream operations whatever B, V and R: one hipMemsetAsync of the
+ * workspace (the ENTRY zeroes it, the caller need not) and three launches; no host synchronisation, no device-to-host copy.
+ * workspace: tmf_region_workspace_bytes(B, V, R) bytes (0 for arguments the entry refuses), 16-byte aligned.
+ *
+ * tmf_region_group_update: values [B][R+1] float (abs_sum, a share, ...; first = 0) or [B][R] for the regions 1..R alone
+ * (occlusion's drops with an atlas; first = 1: bin 0 of the state is not touched), cls [B] int64, state [C][R+1][3] double =
+ * (n, sum x, sum x^2) per class and region, updated in place: ONE launch, one thread per (c, r) walks b in ascending order and
+ * adds 1, x and x*x (x widened to double, the product rounded before it is added) for the samples with cls[b] == c; a sample
+ * with a class outside 0..C-1 is skipped.  No atomics: the bits of that loop in fp64.
+ *
+ * Every pointer 4-byte aligned (cls and state 8-byte), the workspace 16-byte (TMF_E_ALIGN).  Limits (TMF_E_SHAPE / TMF_E_ARG
+ * / TMF_E_WORKSPACE, nothing launched): 1 <= B <= 65536, 1 <= V < 2^31, 1 <= R <= TMF_REGION_MAX, 1 <= C <=
+ * TMF_REGION_MAX_CLASSES. */
+#define TMF_REGION_MAX         1024
+#define TMF_REGION_MAX_CLASSES 16
+size_t tmf_region_workspace_bytes(int B, long V, int R);
+int    tmf_region_stats(const float* a, const int* labels, int* count, float* sum, float* abs_sum, float* pos_sum, float* max_value,
+                        int* argmax, void* workspace, size_t workspace_bytes, int B, long V, int R, void* stream);
+int    tmf_region_group_update(const float* values, const int64_t* cls, double* state, int B, int R, int C, int first,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

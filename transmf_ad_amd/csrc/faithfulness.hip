@@ -10,7 +10,7 @@
 // prefix is one of the at most S selected ones: a workgroup keeps the histograms of FC_GROUP of them in LDS and flushes the
 // same way, the groups share the row through the second grid dimension.  Integer counting only: two calls give the same
 // bits.  Seven stream operations whatever B and V: one memset of the workspace and six launches.
-#include "tmf_common.h"
+#include "tmf_device.h"
 #include <limits.h>
 
 namespace {
@@ -36,15 +36,7 @@ __device__ __forceinline__ unsigned* fc_hist(unsigned* row, int S, int digit) {
 }
 __device__ __forceinline__ unsigned* fc_state(unsigned* row, int S) { return row + FC_BINS + (long)S * FC_BINS + (long)S * (FC_BINS / 2); }
 
-// ascending key <=> ascending a = x + 0.0f as floats (-0.0 ranks with +0.0; infinities are ordinary values)
-__device__ __forceinline__ unsigned fc_key(float x) {
-    unsigned u = __float_as_uint(x);
-    u = u == 0x80000000u ? 0u : u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fc_value(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
+// fc_key / fc_value (tmf_device.h): ascending key <=> ascending a = x + 0.0f as floats
 
 // digit 0: hist0[b][key >> 21] over all voxels of row b.  Workgroup blockIdx.x = b*nblk + blk.
 template <bool VEC>

@@ -99,3 +99,15 @@ __device__ __forceinline__ void split3_rne(float a, unsigned short& h, unsigned 
     const float r2 = r1 - __builtin_bit_cast(float, (unsigned)m << 16);          // exact, fits bf16
     l = bf16_bits_rne(r2);
 }
+
+// ---- the order-preserving uint32 image of a float ------------------------------------------------------------------------------
+// ascending key <=> ascending a = x + 0.0f as floats (-0.0 ranks with +0.0; infinities are ordinary values).  The radix select of
+// faithfulness.hip and the packed max / argmax of region_stats.hip.
+__device__ __forceinline__ unsigned fc_key(float x) {
+    unsigned u = __float_as_uint(x);
+    u = u == 0x80000000u ? 0u : u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float fc_value(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}

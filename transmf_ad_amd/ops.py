@@ -1567,6 +1567,100 @@ def mask_by_rank(vol, attr, thr, fill, mode, j0, K, base=None, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------
+# atlas region statistics (csrc/region_stats.hip; include/tmf_hip.h states the bins, the outputs and the accuracy of the sums)
+# --------------------------------------------------------------------------------------
+
+REGION_MAX = _lib.REGION_MAX
+REGION_MAX_CLASSES = _lib.REGION_MAX_CLASSES
+REGION_FIELDS = ("count", "sum", "abs_sum", "pos_sum", "max", "argmax")
+
+
+def region_ok(*tensors):
+    """The kernels of csrc/region_stats.hip take these: contiguous float32 (int32 labels, int64 classes, float64 state) tensors
+    on one HIP device, none empty."""
+    dev = tensors[0].device
+    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32, torch.int64, torch.float64) and t.is_contiguous()
+               and t.numel() > 0 for t in tensors)
+
+
+def _region_args(a, labels, R):
+    if a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1 or not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor (B, V) with samples and voxels, got {tuple(a.shape)} {a.dtype}")
+    if labels.dim() != 1 or labels.shape[0] != a.shape[1] or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be integers ({a.shape[1]},), got {tuple(labels.shape)} {labels.dtype}")
+    if not isinstance(R, int) or isinstance(R, bool) or R < 1:
+        raise ValueError(f"R must be an integer >= 1, got {R!r}")
+
+
+def region_stats_torch(a, labels, R):
+    """region_stats in stock torch ops on whatever device and dtype `a` has: bincount, index_add_, scatter_reduce("amax") and, for
+    argmax, the minimum index among the voxels equal to the bin's max.  The sums of a dtype narrower than float32 are added up
+    in float32 and rounded once."""
+    _region_args(a, labels, R)
+    B, V = a.shape
+    lab = labels.to(a.device).long()
+    bins = torch.where((lab >= 0) & (lab <= R), lab, torch.zeros_like(lab))
+    count = torch.bincount(bins, minlength=R + 1).to(torch.int32)
+    wide = a if a.dtype in (_f32, torch.float64) else a.float()
+    add = lambda x: torch.zeros((B, R + 1), device=a.device, dtype=wide.dtype).index_add_(1, bins, x).to(a.dtype)
+    rows = bins.view(1, V).expand(B, V)
+    a0 = wide + 0.0
+    mx = torch.full((B, R + 1), float("-inf"), device=a.device, dtype=wide.dtype).scatter_reduce(1, rows, a0, "amax")
+    at = torch.arange(V, device=a.device).view(1, V).expand(B, V)
+    cand = torch.where(a0 == mx.gather(1, rows), at, torch.full_like(at, V))
+    arg = torch.full((B, R + 1), V, device=a.device, dtype=at.dtype).scatter_reduce(1, rows, cand, "amin")
+    arg = torch.where(arg < V, arg, torch.full_like(arg, -1)).to(torch.int32)
+    return count, add(wide), add(wide.abs()), add(wide.clamp(min=0)), mx.to(a.dtype), arg
+
+
+def region_stats(a, labels, R):
+    """a (B, V), labels (V,) integers, R >= 1 -> (count (R+1,) int32, sum, abs_sum, pos_sum, max (B, R+1) of a's dtype, argmax
+    (B, R+1) int32): bin r in 1..R holds the voxels with label r, bin 0 every other voxel; an empty bin has max -inf and argmax -1.
+    Contiguous float32 HIP `a`, int32 labels and R <= REGION_MAX: tmf_region_stats (integer sums: the same bits on every call,
+    no host read); anything else: region_stats_torch."""
+    _region_args(a, labels, R)
+    if not (R <= REGION_MAX and region_ok(a, labels) and a.dtype == _f32 and labels.dtype == torch.int32):
+        return region_stats_torch(a, labels, R)
+    _chk(a, "a")
+    B, V = a.shape
+    count = torch.empty((R + 1,), device=a.device, dtype=torch.int32)
+    outs = [torch.empty((B, R + 1), device=a.device, dtype=_f32) for _ in range(4)]
+    arg = torch.empty((B, R + 1), device=a.device, dtype=torch.int32)
+    nws = _lib.query("tmf_region_workspace_bytes", B, V, R)
+    ws = torch.empty((nws,), device=a.device, dtype=torch.uint8)               # the entry zeroes it
+    _lib.call("tmf_region_stats", a.data_ptr(), labels.data_ptr(), count.data_ptr(), *(t.data_ptr() for t in outs), arg.data_ptr(),
+              ws.data_ptr(), nws, B, V, R, _stream())
+    return (count, *outs, arg)
+
+
+def region_group_update(state, values, cls):
+    """state (C, R+1, 3) float64 = (n, sum x, sum x^2) per class and region += the samples of values by class cls (B,), in
+    ascending b; a class outside 0..C-1 is skipped.  values (B, R+1), or (B, R) for the regions 1..R alone (column 0 of the state
+    is then not touched).  In place.  float32 values, int64 classes and a float64 state, contiguous on one HIP device,
+    C <= REGION_MAX_CLASSES, R <= REGION_MAX: ONE launch (tmf_region_group_update), no atomics; anything else: the same sums
+    by index_add_ in float64."""
+    if state.dim() != 3 or state.shape[2] != 3 or state.dtype != torch.float64 or state.shape[1] < 2:
+        raise ValueError(f"state must be float64 (C, R+1, 3), got {tuple(state.shape)} {state.dtype}")
+    C, R = state.shape[0], state.shape[1] - 1
+    if values.dim() != 2 or values.shape[1] not in (R, R + 1) or values.shape[0] < 1 or tuple(cls.shape) != (values.shape[0],) \
+            or cls.dtype.is_floating_point:
+        raise ValueError(f"values must be (B, {R + 1}) or (B, {R}) and cls integers (B,), got {tuple(values.shape)} and "
+                         f"{tuple(cls.shape)} {cls.dtype}")
+    B, first = values.shape[0], R + 1 - values.shape[1]
+    if C <= REGION_MAX_CLASSES and R <= REGION_MAX and B <= 65536 and region_ok(state, values, cls) and values.dtype == _f32 \
+            and cls.dtype == torch.int64:
+        _chk(values, "values")
+        _lib.call("tmf_region_group_update", values.data_ptr(), cls.data_ptr(), state.data_ptr(), B, R, C, first, _stream())
+        return state
+    x = values.detach().to(device=state.device, dtype=torch.float64)
+    c = cls.to(state.device).long()
+    keep = (c >= 0) & (c < C)
+    x, c = x[keep], c[keep]
+    state[:, first:].index_add_(0, c, torch.stack([torch.ones_like(x), x, x * x], 2))
+    return state
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
