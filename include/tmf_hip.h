@@ -153,6 +153,9 @@ int    tmf_conv3d_fwd_bf16_t(const void* x, const void* w_bf16, void* z, float* 
                              int B, int D, int H, int W, int cin, int cout, int io, void* stream);
 const char* tmf_conv3d_fwd_bf16_kernel_name(int B, int D, int H, int W, int cin, int cout, int io);   /* as tmf_conv3d_fwd_kernel_name */
 const char* tmf_conv3d_wgrad_bf16_kernel_name(int B, int D, int H, int W, int cin, int cout, int io); /* io: 1 = bf16 tensors */
+/* The plan of that launch under the current "wgrad_tr" option (no device call): workgroups per channel block into *nsplit, the
+ * bricks each of them walks into *tiles_per_split; returns the number of 4x8x8 bricks, 0 on bad arguments. */
+int    tmf_conv3d_wgrad_bf16_plan(int B, int D, int H, int W, int cin, int cout, int io, int* nsplit, int* tiles_per_split);
 int    tmf_conv3d_wgrad_bf16_t(const void* x, const void* dz, float* dw, void* workspace, size_t workspace_bytes,
                                int B, int D, int H, int W, int cin, int cout, int io, int dw_layout, void* stream);
 /* fp32-ACCURATE variant on the bf16 matrix cores: operands split exactly into three bf16 numbers (hi+mid+lo), the

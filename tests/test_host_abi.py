@@ -87,6 +87,7 @@ def test_hard_to_parse_prototypes():
     assert pr["tmf_batch_augment"][1][3] is P                     # tmf_augment_decision*: records in device memory
     assert pr["tmf_conv3d_wgrad_wino_tiles"] == (L, [I] * 6) and pr["tmf_conv3d_fwd_kernel_name"] == (C.c_char_p, [I] * 7)
     assert pr["tmf_conv_block_algo"] == (I, [I] * 4)
+    assert pr["tmf_conv3d_wgrad_bf16_plan"] == (I, [I] * 7 + [P, P])              # int* results: host pointers
     with pytest.raises(C.ArgumentError):                          # a wrong struct still raises
         _lib.load().tmf_snet_saved_bytes(C.byref(_lib.FusionDesc()))
 

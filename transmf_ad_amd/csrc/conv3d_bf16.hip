@@ -1720,6 +1720,16 @@ extern "C" const char* tmf_conv3d_wgrad_bf16_kernel_name(int B, int D, int H, in
     return buf;
 }
 
+// the plan of that launch (host arithmetic only, as tmf_conv3d_wino_grid): workgroups per channel block and the bricks each
+// walks; returns the brick count, 0 on bad arguments
+extern "C" int tmf_conv3d_wgrad_bf16_plan(int B, int D, int H, int W, int cin, int cout, int io, int* nsplit, int* tiles_per_split) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || (io != 0 && io != 1) || !nsplit || !tiles_per_split) return 0;
+    const WgBfPlan p = plan_wgrad_bf16(B, D, H, W, cin, cout, io);
+    *nsplit = p.nsplit;
+    *tiles_per_split = p.tps;
+    return p.ntiles;
+}
+
 extern "C" size_t tmf_conv3d_wgrad_bf16_workspace_bytes(int B, int D, int H, int W, int cin, int cout) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return 0;
     size_t need = 0;                                    // no tensor-type argument: enough for either kernel choice
