@@ -1217,7 +1217,8 @@ __global__ __launch_bounds__(NTHR) void conv3d_wino_wgrad_kernel(
 //   * 4 waves, wave = pd: 16 positions x 32 ci x 32 co = 256 accumulator registers (AGPRs);
 //   * a lane (channel l31, tile parity hsel) transforms TWO tiles at once — w origins 4 apart, i.e. 512 bytes apart in the
 //     stage buffer: one ds_read2st64_b32 fetches both into a register pair and the transform runs on v_pk_*_f32
-//     (32 + 8 paired reads and ~64 packed adds per 32 MFMAs: 3.3 instructions per MFMA);
+//     (32 + 8 paired reads and ~64 packed adds per 32 MFMAs: 3.3 instructions per MFMA; W_REUSE: the two h steps of a td share
+//     two of their eight rows — 24 + 8 reads and ~56 packed adds);
 //   * the minus signs of Z = A dz A^T (z3 = -y1 on every axis) are left out of the main loop: position p carries the sign
 //     (-1)^[pd = 3] (-1)^[ph = 3] (-1)^[pw = 3], applied where the kernel turns its sums into dw (G^T dU G per workgroup, once);
 //   * the step of four tiles is two phases of 16 MFMAs: P0 multiplies ph 1, 2 while the rows 0, 3 are read and turned into
@@ -1238,6 +1239,9 @@ __device__ __forceinline__ void static_for(F&& f) {
         f(std::integral_constant<int, N - 1>{});
     }
 }
+#ifndef W_REUSE             // 1: the steps (td, 1) take the w-transformed halo rows 2, 3 over from the steps (td, 0) instead of reading and
+#define W_REUSE 1           // transforming them again (2 of the 8 row transforms per td)
+#endif
 constexpr int WPN = 256;                                          // threads: 4 waves, wave = pd
 // The stage of 16 tiles (a lane's pair = two tiles one ds_read2st64 apart) in two geometries, as in the forward:
 //   GEOM 0: 2 x 2 x 4 tiles of one sample — a 4x4x8 half brick, halo [6][6][10] voxels, the pair 4 voxels apart in w;
@@ -1388,6 +1392,11 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
     };
     f32x2 yq[2][2][2];                              // dz in flight: [slot][ho][wo]
     f32x2 v0[4];
+    // W_REUSE: the halo rows 2, 3 of a plane pair serve both h steps of a td.  Step (td, 0) builds them as its u2 (T1) and its
+    // second v0 (T2); step (td, 1) takes row 3 over as its u1 and row 2 — which its own u2, row 4, overwrites — through k2 as its
+    // first v0.  The steps are unrolled: the hand-over is a renaming, and both steps of a td lie in one stage, so neither the
+    // prologue nor the overhang behind the last stage sees it.  Same numbers from the same instructions: dw keeps every bit.
+    f32x2 k2[4];
     // T1 (three parts, one per group of MFMAs of the phase it rides under): rows 1, 2 of step (td, th) in buffer `par` -> A, B of
     // ph 1, 2; keeps u1, u2 and zd for T2.  dz: z_d = y[do 0] | y0 + y1 | y0 - y1 | y[do 1] for pd = 0 .. 3 = first + cz * second,
     // where pd 3 reads the plane do 1 as its "first" (a wave-uniform address) and cz = 0, 1, -1, 0: no branch
@@ -1395,8 +1404,9 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
         constexpr int STEP = decltype(step_c)::value, TDs = STEP >> 1, THs = STEP & 1;
         if (P_ABL & 1) return;
         const unsigned off = par * WBUF_BYTES;
+        constexpr bool CARRY = W_REUSE && THs == 1;         // u1 = row 3 is here already: the one row read is u2's, a part earlier
         if (part == 0) {
-            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 1) * ROWW>{});
+            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + (CARRY ? 2 : 1)) * ROWW>{});
             static_for<2>([&](auto ho_c) {
                 static_for<2>([&](auto wo_c) {
                     constexpr int HO = decltype(ho_c)::value, WO = decltype(wo_c)::value;
@@ -1406,10 +1416,11 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
                 });
             });
         } else if (part == 1) {
-            row_finish(u1);
+            if (CARRY) lds_wait();                      // (dz; the row waits with it and is transformed under the next group)
+            else row_finish(u1);
             pin4(yq[0][0][0], yq[0][0][1], yq[0][1][0], yq[0][1][1]);
             pin4(yq[1][0][0], yq[1][0][1], yq[1][1][0], yq[1][1][1]);
-            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 2) * ROWW>{});
+            if (!CARRY) row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 2) * ROWW>{});
 #pragma unroll
             for (int ho = 0; ho < 2; ++ho)
 #pragma unroll
@@ -1437,16 +1448,20 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
         constexpr int STEP = decltype(step_c)::value, TDs = STEP >> 1, THs = STEP & 1;
         if (P_ABL & 1) return;
         const unsigned off = par * WBUF_BYTES;
+        constexpr bool CARRY = W_REUSE && THs == 1;         // row 2 is in k2: the one row read is row 5, a part earlier
         if (part == 0) {
-            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 0) * ROWW>{});
+            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + (CARRY ? 3 : 0)) * ROWW>{});
             zrows(zd[0][0], zd[0][1], 0, zd[1][0], zd[1][1], 3);
             pin4(Bv[0], Bv[1], Bv[2], Bv[3]); pin4(Bv[12], Bv[13], Bv[14], Bv[15]);
         } else if (part == 1) {
-            row_finish(v0);
-            row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 3) * ROWW>{});
+            if (!CARRY) {
+                row_finish(v0);
+                row_issue(xa0 + off, xb0 + off, std::integral_constant<int, (2 * TDs) * PLANE + (2 * THs + 3) * ROWW>{});
+            }
             {
                 f32x2 d[4];
-                pk_sub4(d, v0, u2);
+                if constexpr (CARRY) pk_sub4(d, k2, u2);
+                else pk_sub4(d, v0, u2);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) A[k] = d[k];
             }
@@ -1460,6 +1475,10 @@ __global__ __launch_bounds__(WPN) void conv3d_wino_wgrad_p_kernel(
                 for (int k = 0; k < 4; ++k) A[12 + k] = d[k];
             }
             pin4(A[12], A[13], A[14], A[15]);
+            if (W_REUSE && THs == 0) {                  // rows 2, 3 -> step (td, 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { k2[k] = u2[k]; u1[k] = v0[k]; }
+            }
         }
     };
     // a phase's 16 MFMAs (both tile sets of the 8 positions ph in {pha, phb}) in three groups of 4, 4, 8: part g of the other

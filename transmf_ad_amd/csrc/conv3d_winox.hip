@@ -46,6 +46,12 @@
 #ifndef X_RB                // 1: all 16 LDS reads of a (group, buffer) are requested before the first is used (measured level: off)
 #define X_RB 0
 #endif
+#ifndef X_ROLE_FMA          // 1: the epilogue's wave-uniform role selects (which of its two h partials a wave passes on as it is and
+#define X_ROLE_FMA 1        // which as the sum) are FMAs with 0 / 1 coefficients: two instructions per element instead of an add and two selects
+#endif
+#ifndef X_STAT_REG          // 1: MODE 1 keeps the lane's 4 + 4 statistic cells in registers over an item's four stores (one LDS
+#define X_STAT_REG 1        // read and one write per cell and item instead of four read-modify-writes)
+#endif
 #ifndef X_ABL               // timing ablations (tools/build_variant.py --flags=-DX_ABL=n; results are wrong with any bit set):
 #define X_ABL 0             // 1 no input transform, 2 no weight loads, 4 no halo copies, 8 no epilogue, 16 no MFMAs, 32 no split
 #endif
@@ -467,6 +473,9 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
         const int st_lane = ((2 * r_td * sd + 2 * r_th * sh + 2 * r_tw + rwo) * Cout + 4 * cq) * 4;
         float* red_l = red + (wave * 8 + (le >> 3)) * 33 + 4 * cq;
         float* exw = ex + (wave * 32 + (le & 31)) * TS + 4 * (le >> 5);
+#if X_ROLE_FMA
+        const float rc0 = mhh == 0 ? 1.f : 0.f, rc1 = mhh == 0 ? 0.f : 1.f;       // (wave-uniform: scalar registers)
+#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             f32x4 y[2][2];
@@ -481,9 +490,22 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
             }
 #pragma unroll
             for (int wo = 0; wo < 2; ++wo) {
+#if X_ROLE_FMA
+                // p0 = y0 + rc0 y1, P1 = y1 + rc1 y0 with (rc0, rc1) = (1, 0) | (0, 1): fma(1, a, b) rounds as a + b and fma(0, a, b)
+                // is b for every finite a (a zero keeps its value; its sign may differ).  A non-finite y would turn the partial
+                // that does not need it into NaN as well — the sum it also enters is non-finite either way, so an output voxel of
+                // the other ho that the select form left finite is the one place where the results could part.
+                f32x4 p0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    p0[e] = __builtin_fmaf(rc0, y[1][wo][e], y[0][wo][e]);
+                    P1[j][wo][e] = __builtin_fmaf(rc1, y[0][wo][e], y[1][wo][e]);
+                }
+#else
                 const f32x4 sum = y[0][wo] + y[1][wo];
                 const f32x4 p0 = mhh == 0 ? sum : y[0][wo];
                 P1[j][wo] = mhh == 0 ? y[1][wo] : sum;
+#endif
                 *reinterpret_cast<f32x4*>(&exw[wo * 32 + 8 * j]) = p0;
             }
         }
@@ -510,6 +532,7 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
         const int gd0 = d0 + 2 * r_td, gh0 = h0 + 2 * r_th, gw = w0 + 2 * r_tw + rwo;
         const int st_item = ((d0 * sd + h0 * sh + w0) * Cout + n0) * 4;
         const float* exr = ex + (4 * wave + vq) * TS + rwo * 32 + 4 * cq;
+        float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};      // (X_STAT_REG) this lane's statistic cells over the item
         auto pass = [&](int ho) {
             wg_barrier();                                   // (lgkmcnt(0) first: this wave's exchange writes)
             XTR(41 + 4 * ho);
@@ -518,7 +541,7 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
             for (int pd = 0; pd < 4; ++pd) {
                 const f32x4 lo = *reinterpret_cast<const f32x4*>(&exr[(2 * pd) * 32 * TS]);
                 const f32x4 hi = *reinterpret_cast<const f32x4*>(&exr[(2 * pd + 1) * 32 * TS]);
-                S[pd] = ho == 0 ? lo + hi : lo - hi;
+                S[pd] = ho == 0 ? lo + hi : lo - hi;        // (ho is a constant of each of the two inlined passes: no select here)
             }
             f32x4 o[2];
             o[0] = (S[0] + S[1]) + S[2];
@@ -573,12 +596,21 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float v = ok ? o[dd][e] : 0.f;
+#if X_STAT_REG
+                        st_s[e] += v;
+                        st_q[e] += v * v;
+#else
                         red_l[e] += v;
                         red_l[64 * 33 + e] += v * v;
+#endif
                     }
                 }
             }
         };
+        if (STATS && X_STAT_REG) {                          // (the accumulators are dead: the registers exist)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { st_s[e] = red_l[e]; st_q[e] = red_l[64 * 33 + e]; }
+        }
         pass(0);
         XTR(42);
         wg_barrier();                                       // every reader is done with the ho = 0 partials
@@ -589,6 +621,10 @@ __global__ __launch_bounds__(XN) void conv3d_winox_kernel(
             for (int wo = 0; wo < 2; ++wo) *reinterpret_cast<f32x4*>(&exw[wo * 32 + 8 * j]) = P1[j][wo];
         XTR(44);
         pass(1);
+        if (STATS && X_STAT_REG) {                          // the same additions in the same order as cell by cell
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { red_l[e] = st_s[e]; red_l[64 * 33 + e] = st_q[e]; }
+        }
         XTR(46);
         wg_barrier();                                       // the exchange (= halo pair 1) is free for the next item's copies
         XTR(47);
