@@ -1085,6 +1085,64 @@ int    tmf_region_stats(const float* a, const int* labels, int* count, float* su
 int    tmf_region_group_update(const float* values, const int64_t* cls, double* state, int B, int R, int C, int first,
                                void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Connected clusters of voxel maps and the cluster table (csrc/clusters.hip): threshold a map, find its connected clusters,
+ * report each cluster's size, peak, peak voxel, centre and extent.  The reference has no such function; these entries replace a
+ * device-to-host copy and `scipy.ndimage.label` per sample, or a `max_pool3d` propagation loop whose number of launches
+ * depends on the data and which reads a "changed" flag on the host every round.
+ *
+ * tmf_cluster_label.  a [B][D][H][W] float, W fastest; thr [B] float in DEVICE memory (a threshold of tmf_rank_thresholds
+ * needs no host read).  Foreground: a >= thr[b] (TMF_CLUSTER_POS), a <= -thr[b] (TMF_CLUSTER_NEG), |a| >= thr[b]
+ * (TMF_CLUSTER_ABS), compared as floats: a NaN voxel is never foreground, a NaN threshold gives no foreground, -0.0 equals +0.0.
+ * Neighbours.  connectivity 6: the voxels that share a face; 18: a face or an edge; 26: a face, an edge or a corner -
+ * scipy's generate_binary_structure(3, 1 / 2 / 3).  Two foreground voxels lie in one cluster iff a chain of neighbouring
+ * foreground voxels joins them; samples never connect.
+ * Numbering.  Per sample, the clusters with at least min_size voxels are numbered 1, 2, ... in ASCENDING ORDER OF THEIR LOWEST
+ * LINEAR VOXEL INDEX (the order of scipy.ndimage.label); smaller clusters and the background get 0.  labels [B][D][H][W]
+ * int32: EVERY element is written.  n_clusters [B] int32 = the number of surviving clusters, or -1 if a chain-following loop
+ * exceeded its bound (V trips) - that does not happen on a correct build; the labels of that sample are then unspecified.
+ * The result is a function of the inputs alone - not of the grid, the scheduling or the order of arrival: two calls give the
+ * same bits.
+ * How.  Union-find by lowest index: a cluster's root is its lowest linear index, a union points the larger of two roots at the
+ * smaller by an integer atomic min.  One workgroup labels one 8 x 8 x 32 tile in LDS; a second launch unites neighbours across
+ * tile faces in memory (every access to the parents in that launch is a relaxed agent-scope atomic, as another XCD may have
+ * written them); a third follows each voxel's chain to its root into a separate array and counts sizes by integer atomics at
+ * the root; a three-launch prefix sum over V ranks the surviving roots; the last launch writes the labels.  No lane waits for
+ * another workgroup (no flag, no ticket, no look-back), every chain-following loop is bounded.  EIGHT stream operations
+ * whatever B, the data and the number of clusters: one hipMemsetAsync (the ENTRY zeroes the part of the workspace that needs
+ * it, the caller need not) and seven launches; no host synchronisation, no device-to-host copy.
+ * workspace: tmf_cluster_workspace_bytes(B, D, H, W) bytes (8 bytes per voxel and a little; 0 for a shape the entry refuses),
+ * 16-byte aligned.
+ *
+ * tmf_cluster_table.  a as above; labels [B][D][H][W] int32 from tmf_cluster_label or anywhere else: a label outside 1..K is
+ * ignored (the range is checked before any index is formed from it), row k-1 collects the voxels with label k.  s(a) = a (POS),
+ * -a (NEG), |a| (ABS).  Outputs, [B][K] per field, each may be NULL and is then not written:
+ *   size       int32: the voxels of the cluster;
+ *   peak       float: the value a of the voxel `argmax`, bit for bit; NaN (0x7FC00000) for an empty row;
+ *   argmax     int32: the lowest linear index (inside the sample) among the voxels whose s(a) is the row's largest (-0.0 ranks
+ *              with +0.0), -1 for an empty row;
+ *   coord_sum  int64 [B][K][3]: the sums of d, h and w over the cluster (the centroid is exact on the host side);
+ *   bbox       int32 [B][K][6] = min d, min h, min w, max d, max h, max w; (D, H, W, -1, -1, -1) for an empty row.
+ * A NaN voxel inside a labelled cluster makes that row's peak and argmax unspecified; nothing faults.  Integer atomics only
+ * (add, min, max, compare-and-swap), so the bits depend on neither the grid nor the order of arrival.  The entry has no
+ * workspace, so max / argmax is ONE 32-bit word per row: the index of the best voxel so far in the order of
+ * (fc_key(s(a)) << 32) | ~index, raised by compare-and-swap (the key is read back from `a`).  Runs of equal labels inside a wave
+ * are combined by shuffles, then in a 64-slot LDS cache of the workgroup, before memory is touched.  THREE launches whatever
+ * the data (initialise, accumulate, peak values).
+ *
+ * Every pointer 4-byte aligned, coord_sum 8-byte, the workspace 16-byte (TMF_E_ALIGN).  Limits (TMF_E_SHAPE / TMF_E_ARG /
+ * TMF_E_WORKSPACE, nothing launched): 1 <= B <= 65536; D, H, W >= 1 with V = D*H*W < 2^31 (and B * ceil(D/8) * ceil(H/8) *
+ * ceil(W/32), B * ceil(V/2048) and B*K/256 below 2^31: one workgroup each - shapes that do not fit a device's memory anyway);
+ * mode in 0..2; connectivity 6, 18 or 26; min_size >= 1; 1 <= K <= V. */
+#define TMF_CLUSTER_POS 0
+#define TMF_CLUSTER_NEG 1
+#define TMF_CLUSTER_ABS 2
+size_t tmf_cluster_workspace_bytes(int B, int D, int H, int W);
+int    tmf_cluster_label(const float* a, const float* thr, int* labels, int* n_clusters, void* workspace, size_t workspace_bytes,
+                         int B, int D, int H, int W, int mode, int connectivity, int min_size, void* stream);
+int    tmf_cluster_table(const float* a, const int* labels, int* size, float* peak, int* argmax, int64_t* coord_sum, int* bbox,
+                         int B, int D, int H, int W, int mode, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

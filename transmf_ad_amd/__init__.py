@@ -23,6 +23,7 @@ from .gradcam import grad_cam, grad_cam_torch                      # noqa: F401
 from .occlusion import occlusion_sensitivity, occlusion_sensitivity_torch   # noqa: F401
 from .faithfulness import faithfulness_curve, faithfulness_curve_torch   # noqa: F401
 from .region_stats import RegionAccumulator, RegionStats, region_stats, region_stats_torch   # noqa: F401
+from .clusters import Clusters, clusters, clusters_torch       # noqa: F401
 from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, FeedForward, PreNorm,   # noqa: F401
                        Transformer, sNet)
 
@@ -34,4 +35,5 @@ __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_trans
            "input_gradients", "integrated_gradients", "attention_maps", "attention_maps_torch",
            "grad_cam", "grad_cam_torch", "occlusion_sensitivity", "occlusion_sensitivity_torch",
            "faithfulness_curve", "faithfulness_curve_torch",
-           "region_stats", "region_stats_torch", "RegionStats", "RegionAccumulator"]
+           "region_stats", "region_stats_torch", "RegionStats", "RegionAccumulator",
+           "clusters", "clusters_torch", "Clusters"]

@@ -1661,6 +1661,173 @@ def region_group_update(state, values, cls):
     return state
 
 
+# --------------------------------------------------------------------------------------
+# connected clusters and the cluster table (csrc/clusters.hip; include/tmf_hip.h states the foreground, the neighbourhoods, the
+# numbering and the outputs)
+# --------------------------------------------------------------------------------------
+
+CLUSTER_MODES = {"pos": _lib.CLUSTER_POS, "neg": _lib.CLUSTER_NEG, "abs": _lib.CLUSTER_ABS}
+CLUSTER_CONNECTIVITIES = (6, 18, 26)
+
+
+def cluster_ok(*tensors):
+    """The kernels of csrc/clusters.hip take these: contiguous float32 (int32 labels) tensors on one HIP device, none empty."""
+    dev = tensors[0].device
+    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32) and t.is_contiguous() and t.numel() > 0
+               for t in tensors)
+
+
+def _cluster_score(a, mode):
+    return a if mode == "pos" else -a if mode == "neg" else a.abs()
+
+
+def _cluster_label_args(a, thr, mode, connectivity, min_size):
+    if a.dim() != 4 or a.numel() == 0 or not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor (B, D, H, W) with voxels, got {tuple(a.shape)} {a.dtype}")
+    if tuple(thr.shape) != (a.shape[0],) or not thr.dtype.is_floating_point:
+        raise ValueError(f"thr must be a floating-point tensor ({a.shape[0]},), got {tuple(thr.shape)} {thr.dtype}")
+    if mode not in CLUSTER_MODES:
+        raise ValueError(f"mode must be one of {tuple(CLUSTER_MODES)}, got {mode!r}")
+    if connectivity not in CLUSTER_CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {CLUSTER_CONNECTIVITIES}, got {connectivity!r}")
+    if not isinstance(min_size, int) or isinstance(min_size, bool) or min_size < 1:
+        raise ValueError(f"min_size must be an integer >= 1, got {min_size!r}")
+
+
+def _shifted(x, dim, step, fill):
+    """x moved by `step` (+1 / -1) along dim, `fill` where nothing moves in."""
+    n = x.shape[dim]
+    out = torch.full_like(x, fill)
+    if n > 1:
+        out.narrow(dim, max(step, 0), n - 1).copy_(x.narrow(dim, max(-step, 0), n - 1))
+    return out
+
+
+def _min3(x, dim, fill):
+    return torch.minimum(x, torch.minimum(_shifted(x, dim, 1, fill), _shifted(x, dim, -1, fill)))
+
+
+def cluster_label_torch(a, thr, mode="pos", connectivity=26, min_size=1):
+    """cluster_label in stock torch ops on whatever device and dtype `a` has: every foreground voxel starts with its own linear
+    index, takes the minimum over its neighbourhood (shifted copies: the 3 x 3 x 3 cube for 26, the cube without its corners for
+    18, the faces for 6) and jumps to its pointer's pointer, until nothing changes (one host read per round); a root is a voxel
+    that kept its own index, sizes are a scatter_add at the roots, the numbers a cumsum over the surviving roots."""
+    _cluster_label_args(a, thr, mode, connectivity, min_size)
+    B, D, H, W = a.shape
+    V = D * H * W
+    fg = _cluster_score(a, mode) >= thr.to(device=a.device, dtype=a.dtype).view(B, 1, 1, 1)
+    idx = torch.arange(V, device=a.device).view(1, D, H, W).expand(B, D, H, W)
+    big = torch.full_like(idx, V)
+    lab = torch.where(fg, idx, big)
+    flat_fg = fg.reshape(B, V)
+    while True:
+        row = _min3(lab, 3, V)                                          # dw in -1..1
+        plus = torch.minimum(row, torch.minimum(_shifted(lab, 2, 1, V), _shifted(lab, 2, -1, V)))     # |dh| + |dw| <= 1
+        if connectivity == 26:
+            new = _min3(_min3(row, 2, V), 1, V)
+        elif connectivity == 18:
+            new = torch.minimum(_min3(row, 2, V), torch.minimum(_shifted(plus, 1, 1, V), _shifted(plus, 1, -1, V)))
+        else:
+            new = torch.minimum(plus, torch.minimum(_shifted(lab, 1, 1, V), _shifted(lab, 1, -1, V)))
+        new = torch.where(fg, new, big).reshape(B, V)
+        for _ in range(4):                                              # a voxel's pointer lies in its own cluster
+            new = torch.where(flat_fg, new.gather(1, torch.where(flat_fg, new, torch.zeros_like(new))), new)
+        new = new.view(B, D, H, W)
+        if torch.equal(new, lab):
+            break
+        lab = new
+    lab = lab.reshape(B, V)
+    at = torch.where(flat_fg, lab, torch.zeros_like(lab))
+    size = torch.zeros((B, V), device=a.device, dtype=torch.int64).scatter_add_(1, at, flat_fg.long())
+    keep = flat_fg & (lab == idx.reshape(B, V)) & (size >= min_size)
+    number = torch.where(keep, keep.long().cumsum(1), torch.zeros_like(lab))
+    labels = torch.where(flat_fg, number.gather(1, at), torch.zeros_like(lab))
+    return labels.to(torch.int32).view(B, D, H, W), keep.sum(1).to(torch.int32)
+
+
+def cluster_label(a, thr, mode="pos", connectivity=26, min_size=1):
+    """a (B, D, H, W), thr (B,) on a's device -> (labels (B, D, H, W) int32, n (B,) int32): the connected clusters of the voxels
+    with s(a) >= thr[b] (s = a, -a, |a| for mode "pos", "neg", "abs"; NaN is never foreground), neighbours by `connectivity` (6,
+    18, 26), the clusters of at least min_size voxels numbered 1, 2, ... per sample in ascending order of their lowest linear
+    index, everything else 0; n = their number (-1: the kernels hit an internal bound, which a correct build never does).
+    Contiguous float32 HIP tensors: tmf_cluster_label (eight stream operations whatever the data, no host read); anything else:
+    cluster_label_torch."""
+    _cluster_label_args(a, thr, mode, connectivity, min_size)
+    if not (cluster_ok(a, thr) and a.dtype == _f32 and thr.dtype == _f32 and a.shape[0] <= 65536):
+        return cluster_label_torch(a, thr, mode, connectivity, min_size)
+    _chk(a, "a")
+    B, D, H, W = a.shape
+    labels = torch.empty((B, D, H, W), device=a.device, dtype=torch.int32)
+    n = torch.empty((B,), device=a.device, dtype=torch.int32)
+    nws = _lib.query("tmf_cluster_workspace_bytes", B, D, H, W)
+    ws = torch.empty((nws,), device=a.device, dtype=torch.uint8)               # the entry zeroes what needs it
+    _lib.call("tmf_cluster_label", a.data_ptr(), thr.data_ptr(), labels.data_ptr(), n.data_ptr(), ws.data_ptr(), nws, B, D, H, W,
+              CLUSTER_MODES[mode], connectivity, min_size, _stream())
+    return labels, n
+
+
+def _cluster_table_args(a, labels, mode, K):
+    if a.dim() != 4 or a.numel() == 0 or not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor (B, D, H, W) with voxels, got {tuple(a.shape)} {a.dtype}")
+    if tuple(labels.shape) != tuple(a.shape) or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be integers {tuple(a.shape)}, got {tuple(labels.shape)} {labels.dtype}")
+    if mode not in CLUSTER_MODES:
+        raise ValueError(f"mode must be one of {tuple(CLUSTER_MODES)}, got {mode!r}")
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= a[0].numel():
+        raise ValueError(f"K must be an integer in 1..{a[0].numel()} (the voxels of a sample), got {K!r}")
+
+
+def cluster_table_torch(a, labels, mode="pos", K=1):
+    """cluster_table in stock torch ops on whatever device and dtype `a` has: scatter_add for the sizes and the coordinate sums,
+    scatter_reduce("amax" / "amin") for the largest s(a), the lowest index that attains it and the bounding box."""
+    _cluster_table_args(a, labels, mode, K)
+    B, D, H, W = a.shape
+    V = D * H * W
+    dev = a.device
+    lab = labels.to(dev).reshape(B, V).long()
+    valid = (lab >= 1) & (lab <= K)
+    rows = torch.where(valid, lab - 1, torch.full_like(lab, K))                  # column K collects what is ignored
+    flat = a.reshape(B, V)
+    wide = flat if flat.dtype in (_f32, torch.float64) else flat.float()
+    s = _cluster_score(wide, mode) + 0.0
+    idx = torch.arange(V, device=dev).view(1, V).expand(B, V)
+    size = torch.zeros((B, K + 1), device=dev, dtype=torch.int64).scatter_add_(1, rows, torch.ones_like(lab))
+    mx = torch.full((B, K + 1), float("-inf"), device=dev, dtype=wide.dtype).scatter_reduce(1, rows, s, "amax")
+    cand = torch.where(s == mx.gather(1, rows), idx, torch.full_like(idx, V))
+    arg = torch.full((B, K + 1), V, device=dev, dtype=idx.dtype).scatter_reduce(1, rows, cand, "amin")[:, :K]
+    found = arg < V
+    peak = torch.where(found, flat.gather(1, arg.clamp(max=V - 1)), torch.full_like(flat[:, :1], float("nan")).expand(B, K))
+    coords = torch.stack([idx // (H * W), idx // W % H, idx % W], 2)             # (B, V, 3)
+    rows3 = rows.view(B, V, 1).expand(B, V, 3)
+    coord_sum = torch.zeros((B, K + 1, 3), device=dev, dtype=torch.int64).scatter_add_(1, rows3, coords)[:, :K]
+    start = torch.tensor([D, H, W], device=dev).view(1, 1, 3).expand(B, K + 1, 3).contiguous()
+    lo = start.scatter_reduce(1, rows3, coords, "amin")[:, :K]
+    hi = torch.full((B, K + 1, 3), -1, device=dev, dtype=torch.int64).scatter_reduce(1, rows3, coords, "amax")[:, :K]
+    return (size[:, :K].to(torch.int32), peak.contiguous(), torch.where(found, arg, torch.full_like(arg, -1)).to(torch.int32),
+            coord_sum.contiguous(), torch.cat([lo, hi], 2).to(torch.int32))
+
+
+def cluster_table(a, labels, mode="pos", K=1):
+    """a (B, D, H, W), labels (B, D, H, W) integers, K >= 1 -> (size (B, K) int32, peak (B, K) of a's dtype, argmax (B, K) int32,
+    coord_sum (B, K, 3) int64, bbox (B, K, 6) int32): row k-1 describes the voxels with label k (a label outside 1..K is
+    ignored) - their number, the value of the voxel whose s(a) is largest (NaN for an empty row), the lowest linear index of such
+    a voxel (-1), the sums of d, h, w and (min d, min h, min w, max d, max h, max w) ((D, H, W, -1, -1, -1)).  Contiguous float32
+    HIP `a` and int32 labels: tmf_cluster_table (three launches, integer atomics: the same bits on every call); anything else:
+    cluster_table_torch."""
+    _cluster_table_args(a, labels, mode, K)
+    B = a.shape[0]
+    if not (cluster_ok(a, labels) and a.dtype == _f32 and labels.dtype == torch.int32 and B <= 65536 and B * K < 1 << 31):
+        return cluster_table_torch(a, labels, mode, K)
+    _chk(a, "a")
+    size, arg = (torch.empty((B, K), device=a.device, dtype=torch.int32) for _ in range(2))
+    peak = torch.empty((B, K), device=a.device, dtype=_f32)
+    coord_sum = torch.empty((B, K, 3), device=a.device, dtype=torch.int64)
+    bbox = torch.empty((B, K, 6), device=a.device, dtype=torch.int32)
+    _lib.call("tmf_cluster_table", a.data_ptr(), labels.data_ptr(), size.data_ptr(), peak.data_ptr(), arg.data_ptr(),
+              coord_sum.data_ptr(), bbox.data_ptr(), B, *a.shape[1:], CLUSTER_MODES[mode], K, _stream())
+    return size, peak, arg, coord_sum, bbox
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer
