@@ -45,6 +45,8 @@ def test_torch_formulas_against_a_python_loop(kind):
     rthr, rrem = fi.thresholds_ref(attr, counts)
     assert thr.dtype == attr.dtype and removed.dtype == torch.int32 and thr.shape == removed.shape == (B, S)
     assert torch.equal(fi.bits(thr), fi.bits(rthr)) and torch.equal(removed, rrem)
+    forced = ops.rank_thresholds_torch(attr.view(B, 1, 1, 1, V), counts)                  # the forced form: same formula
+    assert torch.equal(fi.bits(forced[0]), fi.bits(thr)) and torch.equal(forced[1], removed)
     for b in range(B):
         bt, br = fi.thresholds_brute(attr[b].tolist(), counts)
         assert thr[b].tolist() == bt and removed[b].tolist() == br
@@ -57,6 +59,7 @@ def test_torch_formulas_against_a_python_loop(kind):
             for j0, K in fi.chunkings(B, S):
                 got = ops.mask_by_rank(vol, attr, thr, fill, mode, j0, K, base=bs)
                 assert torch.equal(got, fi.mask_ref(vol, attr, thr, fill, mode, j0, K, base=bs))
+                assert torch.equal(ops.mask_by_rank_torch(vol, attr, thr, fill, mode, j0, K, base=bs), got)
                 for k in range(K):
                     b, s = divmod(j0 + k, S + 1)
                     for e in range(V):
@@ -70,11 +73,13 @@ def test_torch_formulas_against_a_python_loop(kind):
                 dict(attr=attr[:, :-1]), dict(base=base[:, :-1]), dict(out=torch.empty((2, V)))):
         kw = dict(vol=vol, attr=attr, thr=thr, fill=fill, mode="deletion", j0=0, K=1)
         kw.update(bad)
-        with pytest.raises(ValueError):
-            ops.mask_by_rank(**kw)
+        for fn in (ops.mask_by_rank, ops.mask_by_rank_torch):
+            with pytest.raises(ValueError):
+                fn(**kw)
     for bad in ([], [0, 1], [2, 1], [1, V + 1], list(range(1, 66))):
-        with pytest.raises(ValueError):
-            ops.rank_thresholds(attr, bad)
+        for fn in (ops.rank_thresholds, ops.rank_thresholds_torch):
+            with pytest.raises(ValueError):
+                fn(attr, bad)
 
 
 class _Sum(nn.Module):

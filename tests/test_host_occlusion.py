@@ -102,6 +102,7 @@ def test_torch_formulas_against_brute_force(case):
         want = oi.occlude_ref(vol, fill, patch, stride, j0, K)
         got = ops.occlude_windows(vol, fill, patch, stride, j0, K)
         assert got.shape == (K, 1) + size and torch.equal(got, want)
+        assert torch.equal(ops.occlude_windows_torch(vol, fill, patch, stride, j0, K), want)      # the forced form: same formula
         assert int((got != vol[(torch.arange(j0, j0 + K) // nW)]).sum()) > 0
         buf = torch.full((K, 1) + size, 9.0)
         assert ops.occlude_windows(vol, fill, patch, stride, j0, K, out=buf) is buf and torch.equal(buf, want)
@@ -121,10 +122,11 @@ def test_torch_formulas_against_brute_force(case):
         assert float(oi.row_errors(got, ref).max()) <= oi.volume_tolerance(case) / oi.MARGIN * 2
     got64 = ops.occlusion_volume(drops.double(), size, patch, stride)
     assert float(oi.row_errors(got64, ref).max()) <= 1e-15
-    with pytest.raises(ValueError):
-        ops.occlude_windows(vol, fill, patch, stride, B * nW, 1)
-    with pytest.raises(ValueError):
-        ops.occlude_windows(vol, fill[:0], patch, stride, 0, 1)
+    for fn in (ops.occlude_windows, ops.occlude_windows_torch):
+        with pytest.raises(ValueError):
+            fn(vol, fill, patch, stride, B * nW, 1)
+        with pytest.raises(ValueError):
+            fn(vol, fill[:0], patch, stride, 0, 1)
     with pytest.raises(ValueError):
         ops.occlusion_volume(drops[:, :-1] if nW > 1 else torch.zeros(B, 2), size, patch, stride)
 
@@ -145,6 +147,7 @@ def test_atlas_formulas(size, R):
     for j0, K in oi.chunkings(B, R):
         want = oi.occlude_labels_ref(vol, lab, fill, R, j0, K)
         assert torch.equal(ops.occlude_labels(vol, lab, fill, R, j0, K), want)
+        assert torch.equal(ops.occlude_labels_torch(vol, lab, fill, R, j0, K), want)
     absent = ops.occlude_labels(vol, lab, fill, R, oi.ATLAS_ABSENT - 1, 1)
     assert torch.equal(absent[0], vol[0])                                   # a region without voxels: the volume itself
     every = torch.stack([ops.occlude_labels(vol, lab, fill, R, r, 1)[0] for r in range(R)])
@@ -153,8 +156,9 @@ def test_atlas_formulas(size, R):
     drops = oi.drops_for(B, R, seed=1) + 1.0
     got = ops.occlusion_volume(drops, size, labels=lab)
     assert torch.equal(got, oi.volume_labels_ref(drops, lab, R)) and bool((got[:, outside] == 0).all())
-    with pytest.raises(ValueError):
-        ops.occlude_labels(vol, lab.float(), fill, R, 0, 1)
+    for fn in (ops.occlude_labels, ops.occlude_labels_torch):
+        with pytest.raises(ValueError):
+            fn(vol, lab.float(), fill, R, 0, 1)
     with pytest.raises(ValueError):
         ops.occlusion_volume(drops, size, labels=lab[:-1])
 

@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import networks, ops
+from ._explain import _trilinear
 
 __all__ = ["attention_maps", "attention_maps_torch", "AttentionMaps", "token_grid"]
 
@@ -42,15 +43,12 @@ class AttentionMaps:
         (B, heads, *size) for heads=None."""
         if self.grid is None:
             raise ValueError("these maps were computed from tokens alone: no token grid to lay them out on")
-        size = self.size if size is None else tuple(int(s) for s in size)
-        if size is None or len(size) != 3:
-            raise ValueError(f"size must be three spatial extents, got {size!r}")
         r = self.received[layer, direction]                       # (B, heads, N)
         if heads == "mean":
             r = r.mean(1, keepdim=True)
         elif heads is not None:
             r = r[:, int(heads)].unsqueeze(1)
-        vol = F.interpolate(r.reshape(r.shape[0], r.shape[1], *self.grid), size=size, mode="trilinear", align_corners=False)
+        vol = _trilinear(r.reshape(r.shape[0], r.shape[1], *self.grid), size, self.size)
         return vol if heads is None else vol[:, 0]
 
 

@@ -24,12 +24,12 @@ Contiguous float32 maps on a HIP device take the kernels (ops.cluster_label: tmf
 the data; ops.cluster_table: tmf_cluster_table, three launches; csrc/clusters.hip; no host synchronisation in either); every
 other tensor - another dtype or layout, the CPU - takes ops.cluster_label_torch and ops.cluster_table_torch, the same functions
 in stock torch ops, which return identical integers."""
-import contextlib
 import math
 
 import torch
 
 from . import ops
+from ._explain import _attribution, _dhw, _int, _on, _peak_voxel
 from .region_stats import region_stats, region_stats_torch
 
 __all__ = ["clusters", "clusters_torch", "Clusters"]
@@ -51,12 +51,7 @@ class Clusters:
 
     def peak_voxel(self, k):
         """(B, 3) int64: the (d, h, w) of cluster k's peak, (-1, -1, -1) where the row is empty."""
-        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= self.K:
-            raise ValueError(f"k must be a cluster in 1..{self.K}, got {k!r}")
-        i = self.argmax[:, k - 1].long()
-        _D, H, W = self.shape
-        zyx = torch.stack([i // (H * W), i // W % H, i % W], 1)
-        return torch.where((i >= 0).view(-1, 1), zyx, torch.full_like(zyx, -1))
+        return _peak_voxel(self.argmax[:, _int(k, f"k must be a cluster in 1..{self.K}", 1, self.K) - 1], self.shape)
 
     def order(self, by="size"):
         """(B, K) int64 cluster numbers: the largest first by "size", or the highest s(peak) first by "peak"; ties: the lower
@@ -73,9 +68,7 @@ class Clusters:
     def stats(self, attribution):
         """A list of B RegionStats: region_stats(attribution[b:b+1], labels[b], R=min(K, ops.REGION_MAX)) - the sums of ANY map
         of the same shape per cluster of sample b (bin 0: everything outside the clusters 1..R)."""
-        a = _as_volumes(attribution)
-        if tuple(a.shape) != tuple(self.labels.shape):
-            raise ValueError(f"attribution must hold {tuple(self.labels.shape)} voxels, got {tuple(attribution.shape)}")
+        a = _attribution(attribution, self.labels.shape)
         fn = region_stats_torch if self._torch_only else region_stats
         return [fn(a[b:b + 1], self.labels[b], R=min(self.K, ops.REGION_MAX)) for b in range(a.shape[0])]
 
@@ -83,7 +76,6 @@ class Clusters:
         """One host copy -> a list of dict rows (sample, cluster, size, peak, peak_voxel, centroid, bbox), sample-major, empty
         rows left out."""
         B, K = self.size.shape
-        _D, H, W = self.shape
         host = torch.cat([self.size.double().unsqueeze(2), self.peak.double().unsqueeze(2), self.argmax.double().unsqueeze(2),
                           self.centroid, self.bbox.double()], 2).cpu()
         rows = []
@@ -92,22 +84,13 @@ class Clusters:
                 n, peak, arg = int(host[b, k, 0]), float(host[b, k, 1]), int(host[b, k, 2])
                 if n == 0:
                     continue
-                rows.append(dict(sample=b, cluster=k + 1, size=n, peak=peak, peak_voxel=(arg // (H * W), arg // W % H, arg % W),
+                rows.append(dict(sample=b, cluster=k + 1, size=n, peak=peak, peak_voxel=_dhw(arg, self.shape),
                                  centroid=tuple(float(x) for x in host[b, k, 3:6]), bbox=tuple(int(x) for x in host[b, k, 6:12])))
         return rows
 
 
-def _as_volumes(attribution):
-    if not torch.is_tensor(attribution) or not attribution.dtype.is_floating_point or attribution.dim() not in (4, 5) \
-            or (attribution.dim() == 5 and attribution.shape[1] != 1) or attribution.numel() == 0:
-        raise ValueError("attribution must be a floating-point tensor (B, D, H, W) or (B, 1, D, H, W) with voxels, got "
-                         f"{tuple(attribution.shape) if torch.is_tensor(attribution) else attribution!r}")
-    a = attribution.detach()
-    return a[:, 0] if a.dim() == 5 else a
-
-
 def _run(attribution, threshold, top, mode, connectivity, min_size, max_clusters, torch_only):
-    a = _as_volumes(attribution)
+    a = _attribution(attribution)
     B, V = a.shape[0], a[0].numel()
     if (threshold is None) == (top is None):
         raise ValueError("exactly one of threshold and top must be given")
@@ -115,10 +98,9 @@ def _run(attribution, threshold, top, mode, connectivity, min_size, max_clusters
         raise ValueError(f"mode must be one of {tuple(ops.CLUSTER_MODES)}, got {mode!r}")
     if connectivity not in ops.CLUSTER_CONNECTIVITIES:
         raise ValueError(f"connectivity must be one of {ops.CLUSTER_CONNECTIVITIES}, got {connectivity!r}")
-    if not isinstance(min_size, int) or isinstance(min_size, bool) or min_size < 1:
-        raise ValueError(f"min_size must be an integer >= 1, got {min_size!r}")
-    if max_clusters is not None and (not isinstance(max_clusters, int) or isinstance(max_clusters, bool) or max_clusters < 1):
-        raise ValueError(f"max_clusters must be None or an integer >= 1, got {max_clusters!r}")
+    _int(min_size, "min_size must be an integer >= 1", 1)
+    if max_clusters is not None:
+        _int(max_clusters, "max_clusters must be None or an integer >= 1", 1)
     if top is not None and (isinstance(top, bool) or not isinstance(top, (int, float)) or not 0 < top <= 1):
         raise ValueError(f"top must be a fraction in (0, 1], got {top!r}")
     if threshold is not None and torch.is_tensor(threshold):
@@ -128,7 +110,7 @@ def _run(attribution, threshold, top, mode, connectivity, min_size, max_clusters
         raise ValueError(f"threshold must be a number or a ({B},) tensor, got {threshold!r}")
     kernels = not torch_only and a.is_contiguous()
     thr_dtype = torch.float32 if a.dtype != torch.float64 else torch.float64
-    with torch.no_grad(), (torch.cuda.device(a.device) if a.is_cuda else contextlib.nullcontext()):
+    with torch.no_grad(), _on(a):
         if top is not None:
             count = min(V, max(1, math.ceil(top * V)))
             s = ops._cluster_score(a, mode).reshape(B, V)

@@ -33,20 +33,16 @@ The thresholds come from ONE call (ops.rank_thresholds: tmf_rank_thresholds, csr
 sort).  The jobs are walked in chunks of `chunk`: ONE launch (ops.mask_by_rank: tmf_mask_by_rank) writes the chunk's masked
 volumes into a buffer allocated once, one model(...) call runs, the scores come from the (K, classes) logits by torch ops.
 
-reuse=True is occlusion's machinery as it stands (occlusion._baseline, occlusion._Replay): every networks.sNet of a package
+reuse=True is the machinery occlusion uses (_explain._baseline, _explain._Replay): every networks.sNet of a package
 model that ran once in the unmasked forward, on a volume argument other than `volume`, keeps its output and replays it
 through sNet.tmf_replay for the pass, taken off again also when the model raises.
 
 faithfulness_curve_torch is the same function on sort(descending=True), a gather, >= and torch.where, on any device and
 dtype and any nn.Module (the reference's classes on the CPU in float or double); tmf_replay is not used there."""
-import contextlib
-
 import torch
-from torch import nn
 
 from . import ops
-from .occlusion import SCORES, _Replay, _baseline, _score
-from .saliency import _check, _logits, _resolve_target
+from ._explain import _attribution, _fill, _int, _on, _pass_arguments, _Pass
 
 __all__ = ["faithfulness_curve", "faithfulness_curve_torch", "Faithfulness", "MODES"]
 
@@ -63,52 +59,17 @@ class Faithfulness:
         self.steps, self.mode, self.volume = steps, mode, volume
 
 
-def _fill(fill, v, B):
-    msg = f"fill must be a float, \"mean\" or a tensor ({B},), got {fill!r}"
-    if isinstance(fill, str):
-        if fill != "mean":
-            raise ValueError(msg)
-        return v.reshape(B, -1).mean(1)
-    if torch.is_tensor(fill):
-        if tuple(fill.shape) != (B,):
-            raise ValueError(f"a fill tensor must be ({B},), got {tuple(fill.shape)}")
-        return fill.detach().to(device=v.device, dtype=v.dtype).contiguous()
-    if isinstance(fill, (int, float)) and not isinstance(fill, bool):
-        return torch.full((B,), float(fill), device=v.device, dtype=v.dtype)
-    raise ValueError(msg)
-
-
 def _run(model, volumes, attribution, volume, steps, mode, fill, baseline, score, target, output, chunk, reuse, torch_only):
-    _check(volumes)
-    if not isinstance(model, nn.Module):
-        raise TypeError(f"faithfulness_curve: {type(model).__name__} is not an nn.Module")
-    if any(m.training for m in model.modules()):
-        raise ValueError("faithfulness_curve explains the deployed network: call model.eval() first (train-mode BatchNorm "
-                         "would mix the jobs of a chunk)")
-    if score not in SCORES:
-        raise ValueError(f"score must be one of {SCORES}, got {score!r}")
+    vols, B = _pass_arguments("faithfulness_curve", "jobs", model, volumes, score, chunk)
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-    if not isinstance(steps, int) or isinstance(steps, bool) or not 1 <= steps <= 64:
-        raise ValueError(f"steps must be an integer in 1..64, got {steps!r}")
-    if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, got {chunk!r}")
-    vols = [v.detach() for v in volumes]
-    if not isinstance(volume, int) or isinstance(volume, bool) or not 0 <= volume < len(vols):
-        raise ValueError(f"volume must name one of the {len(vols)} volume arguments, got {volume!r}")
-    B = vols[0].shape[0]
-    if any(v.dim() < 4 or v.shape[0] != B for v in vols):
-        raise ValueError("volumes must be (B, ..., D, H, W) with one batch size")
-    v = vols[volume]
+    S = _int(steps, "steps must be an integer in 1..64", 1, 64)
+    v = vols[_int(volume, f"volume must name one of the {len(vols)} volume arguments", 0, len(vols) - 1)]
     size = tuple(int(s) for s in v.shape[-3:])
     V = size[0] * size[1] * size[2]
     if B < 1 or V < 1 or v.numel() != B * V:
         raise ValueError("the masked volume must be a one-channel volume (B, 1, D, H, W) with voxels")
-    if not torch.is_tensor(attribution) or not attribution.dtype.is_floating_point \
-            or tuple(attribution.shape) not in ((B,) + size, (B, 1) + size):
-        raise ValueError(f"attribution must be a floating-point tensor ({B}, {size[0]}, {size[1]}, {size[2]}) or with a channel "
-                         f"axis of 1, got {tuple(attribution.shape) if torch.is_tensor(attribution) else attribution!r}")
-    attr = attribution.detach().to(v.device).contiguous()
+    attr = _attribution(attribution, (B,) + size).to(v.device).contiguous()
     if bool(torch.isnan(attr).any()):                                   # the one host read
         raise ValueError("attribution holds NaN: voxels cannot be ranked")
     base_vol = None
@@ -117,76 +78,19 @@ def _run(model, volumes, attribution, volume, steps, mode, fill, baseline, score
             raise ValueError(f"baseline must be a tensor of the volume's shape {tuple(v.shape)}")
         base_vol = baseline.detach().to(device=v.device, dtype=v.dtype).contiguous()
     fills = _fill(fill, v, B)
-    counts = ops.rank_counts(V, steps)
-    S, nJ = steps, B * (steps + 1)
+    counts = ops.rank_counts(V, S)
+    thresholds, mask = (ops.rank_thresholds_torch, ops.mask_by_rank_torch) if torch_only else (ops.rank_thresholds, ops.mask_by_rank)
 
-    def thresholds():
-        if not torch_only:
-            return ops.rank_thresholds(attr, counts)
-        a = attr.reshape(B, V) + 0.0
-        srt = a.sort(1, descending=True).values
-        thr = srt.gather(1, torch.tensor(counts, device=a.device).view(1, S).expand(B, S) - 1)
-        return thr, torch.stack([(a >= thr[:, k:k + 1]).sum(1) for k in range(S)], 1).to(torch.int32)
-
-    def masked(thr, j0, K, out):
-        if not torch_only:
-            return ops.mask_by_rank(v, attr, thr, fills, mode, j0, K, base=base_vol, out=out)
-        a = attr.reshape(v.shape) + 0.0
-        xs = []
-        for j in range(j0, j0 + K):                                     # torch.where, as a user writes it
-            b, s = divmod(j, S + 1)
-            m = a[b] >= thr[b, s - 1] if s else torch.zeros_like(a[b], dtype=torch.bool)
-            f = base_vol[b] if base_vol is not None else fills[b]
-            xs.append(torch.where(m, f, v[b]) if mode == "deletion" else torch.where(m, v[b], f))
-        return torch.stack(xs)
-
-    # the library launches on the CURRENT device's current stream: make the volumes' device current for the duration
-    guard = torch.cuda.device(vols[0].device) if vols[0].is_cuda else contextlib.nullcontext()
-    with torch.no_grad(), guard:
-        logits, encoders = _baseline(model, vols, output, reuse and not torch_only)
-        target = _resolve_target(target, logits)
-        base = _score(logits, target, score)
-        sides = []
-        if logits.is_cuda:
-            # the two-encoder models run one encoder on a side stream: order it ahead of the reads of its kept output
-            from . import mymodel
-            cur = torch.cuda.current_stream(logits.device)
-            sides = mymodel.backward_streams(logits.device)
-            for s in sides:
-                cur.wait_stream(s)
-            for encs in encoders.values():
-                for _enc, out in encs:
-                    out.record_stream(cur)
-        thr, removed = thresholds()
-        kept = [e for i, encs in encoders.items() if i != volume for e in encs]
-        replayed = {i for i in encoders if i != volume}
+    with torch.no_grad(), _on(vols[0]):
+        run = _Pass(model, vols, score, target, output, chunk, reuse)
+        thr, removed = thresholds(attr, counts)
         # the chunk buffer of the kernel path, allocated once per pass (the torch ops allocate as they go)
-        tensors = (v, attr, thr) + ((base_vol,) if base_vol is not None else (fills,))
-        buf = torch.empty((min(chunk, nJ),) + tuple(v.shape[1:]), device=v.device, dtype=v.dtype) \
-            if not torch_only and ops.faithfulness_ok(*tensors) else None
-        scores = torch.empty((nJ,), device=logits.device, dtype=logits.dtype)
-        with _Replay(kept) as replay:
-            for j0 in range(0, nJ, chunk):
-                K = min(chunk, nJ - j0)
-                rows = torch.arange(j0, j0 + K, device=logits.device) // (S + 1)
-                batch = []
-                for i, x in enumerate(vols):
-                    if i == volume:
-                        batch.append(masked(thr, j0, K, None if buf is None else buf[:K]))
-                    elif i in replayed:
-                        batch.append(x[:1].expand(K, *x.shape[1:]))        # not read: its encoder replays
-                    else:
-                        batch.append(x.index_select(0, rows.to(x.device)))
-                replay.set(rows)
-                out = _logits(model, batch, output)
-                scores[j0:j0 + K] = _score(out, target.index_select(0, rows), score)
-        if buf is not None:
-            for s in sides:
-                buf.record_stream(s)
-        scores = scores.view(B, S + 1)
+        buffered = not torch_only and ops.faithfulness_ok(v, attr, thr, base_vol if base_vol is not None else fills)
+        masked = lambda _i, j0, K, out: mask(v, attr, thr, fills, mode, j0, K, base=base_vol, out=out)
+        scores = run.scores((volume,), S + 1, masked, (volume,) if buffered else ()).view(B, S + 1)
         auc = (scores[:, 0] / 2 + scores[:, 1:S].sum(1) + scores[:, S] / 2) / S
         removed = torch.cat([torch.zeros((B, 1), device=removed.device, dtype=removed.dtype), removed], 1)
-    return Faithfulness(scores, auc, removed, thr, logits, target, base, S, mode, volume)
+    return Faithfulness(scores, auc, removed, thr, run.logits, run.target, run.base, S, mode, volume)
 
 
 def faithfulness_curve(model, *vols, attribution, volume=0, steps=20, mode="deletion", fill=0.0, baseline=None, score="prob",

@@ -33,11 +33,10 @@ It also takes modules that are not this package's — the reference's classes on
 with conv1 ... conv4 Sequentials counts as an encoder and is tapped with ordinary forward hooks on those Sequentials and their
 [2] children."""
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from . import networks, ops
-from .saliency import _check, _Frozen, _logits, _resolve_target
+from ._explain import _check, _Frozen, _join_side_streams, _logits, _on, _resolve_target, _trilinear
 
 __all__ = ["grad_cam", "grad_cam_torch", "GradCams", "LAYERS", "METHODS"]
 
@@ -97,11 +96,7 @@ class GradCams:
     def volume(self, encoder=None, layer=None, size=None):
         """The map resampled to `size` (default: the input volumes' shape) by trilinear interpolation, align_corners=False
         -> (B, *size)."""
-        size = self.size if size is None else tuple(int(s) for s in size)
-        if size is None or len(size) != 3:
-            raise ValueError(f"size must be three spatial extents, got {size!r}")
-        m = self.map(encoder, layer)
-        return F.interpolate(m.unsqueeze(1), size=size, mode="trilinear", align_corners=False)[:, 0]
+        return _trilinear(self.map(encoder, layer).unsqueeze(1), size, self.size)[:, 0]
 
 
 def resolve_layers(layer):
@@ -188,20 +183,13 @@ def _run(model, volumes, layer, method, target, output, relu, normalize, torch_o
     for i, k in enumerate(keys):
         if k in taps.channels_first:
             acts[i], grads[i] = acts[i].permute(0, 2, 3, 4, 1), grads[i].permute(0, 2, 3, 4, 1)
-    if logits.is_cuda:
-        # the two-encoder models run one encoder (forward and backward) on a side stream: order it ahead of what follows here
-        from . import mymodel
-        cur = torch.cuda.current_stream(logits.device)
-        for s in mymodel.backward_streams(logits.device):
-            cur.wait_stream(s)
-        for t in acts + grads:
-            if t.is_cuda:
-                t.record_stream(cur)
+    # the two-encoder models run one encoder (forward and backward) on a side stream: order it ahead of what follows here
+    _join_side_streams(logits, acts + grads)
     maps, weights, peaks = {}, {}, {}
     for key, a, g in zip(keys, acts, grads):
         a, g = a.contiguous(), g.contiguous()
         if not torch_only and ops.cam_ok(a, g):
-            with torch.cuda.device(a.device):
+            with _on(a):
                 maps[key], weights[key], peaks[key] = ops.cam(a, g, method, relu, normalize)
         else:
             if a.dtype in (torch.bfloat16, torch.float16):

@@ -39,29 +39,19 @@ this package's model class, or joint=True over all volumes has nothing to reuse.
 
 occlusion_sensitivity_torch is the same function with clone and slice assignment and the voxel map in plain torch ops, on any
 device and dtype and any nn.Module (the reference's classes on the CPU in float or double); tmf_replay is not used there."""
-import contextlib
-
 import torch
-from torch import nn
 
-from . import networks, ops
-from .saliency import _check, _logits, _resolve_target
+from . import ops
+from ._explain import SCORES, _fill, _is_int, _on, _pass_arguments, _Pass
 
 __all__ = ["occlusion_sensitivity", "occlusion_sensitivity_torch", "Occlusion", "SCORES"]
 
-SCORES = ("logit", "prob")
-
 
 def _triple(v, name):
-    t = (v,) * 3 if isinstance(v, int) and not isinstance(v, bool) else tuple(v) if isinstance(v, (tuple, list)) else None
-    if t is None or len(t) != 3 or any(not isinstance(x, int) or isinstance(x, bool) or x < 1 for x in t):
+    t = (v,) * 3 if _is_int(v) else tuple(v) if isinstance(v, (tuple, list)) else None
+    if t is None or len(t) != 3 or any(not _is_int(x) or x < 1 for x in t):
         raise ValueError(f"{name} must be a positive int or three of them, got {v!r}")
     return t
-
-
-def _score(logits, target, score):
-    s = logits if score == "logit" else torch.softmax(logits, 1)
-    return s.gather(1, target.view(-1, 1))[:, 0]
 
 
 class Occlusion:
@@ -93,71 +83,11 @@ class Occlusion:
         return self._maps[self._key(volume)]
 
 
-class _Replay:
-    """sNet.tmf_replay on the given encoders for one pass; taken off again on exit."""
-
-    def __init__(self, encoders):
-        self.encoders = encoders
-
-    def __enter__(self):
-        return self
-
-    def set(self, rows):
-        for enc, base in self.encoders:
-            enc.tmf_replay = base.index_select(0, rows)
-
-    def __exit__(self, *exc):
-        for enc, _base in self.encoders:
-            enc.tmf_replay = None
-        return False
-
-
-def _baseline(model, vols, output, want_reuse):
-    """The unoccluded forward -> (logits, {volume index: [(encoder, channels-last baseline output)]}): every sNet that ran
-    exactly once, on one of the volume arguments as it stands."""
-    seen, hooks = {}, []
-    if want_reuse:
-        from . import mymodel
-        if isinstance(model, mymodel._FastModeSwitch):
-            def hook(mod, args, kwargs, out):
-                seen.setdefault(mod, []).append((args[0] if args else next(iter(kwargs.values()), None), out))
-            hooks = [m.register_forward_hook(hook, with_kwargs=True) for m in model.modules() if isinstance(m, networks.sNet)]
-    try:
-        logits = _logits(model, vols, output)
-    finally:
-        for h in hooks:
-            h.remove()
-    by_volume = {}
-    for enc, runs in seen.items():
-        if len(runs) != 1 or not torch.is_tensor(runs[0][0]) or getattr(enc, "tmf_replay", None) is not None:
-            continue
-        inp, out = runs[0]
-        for i, v in enumerate(vols):
-            if inp.data_ptr() == v.data_ptr() and inp.shape == v.shape and inp.stride() == v.stride():
-                by_volume.setdefault(i, []).append((enc, out.permute(0, 2, 3, 4, 1)))      # back to (B, d, h, w, C)
-                break
-    return logits, by_volume
-
-
 def _run(model, volumes, patch, stride, atlas, fill, score, target, output, which, joint, chunk, reuse, torch_only):
-    _check(volumes)
-    if not isinstance(model, nn.Module):
-        raise TypeError(f"occlusion_sensitivity: {type(model).__name__} is not an nn.Module")
-    if any(m.training for m in model.modules()):
-        raise ValueError("occlusion_sensitivity explains the deployed network: call model.eval() first (train-mode BatchNorm "
-                         "would mix the windows of a chunk)")
-    if score not in SCORES:
-        raise ValueError(f"score must be one of {SCORES}, got {score!r}")
-    if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, got {chunk!r}")
-    vols = [v.detach() for v in volumes]
+    vols, B = _pass_arguments("occlusion_sensitivity", "windows", model, volumes, score, chunk)
     which = tuple(range(len(vols))) if which is None else (which,) if isinstance(which, int) else tuple(which)
-    if not which or any(not isinstance(i, int) or isinstance(i, bool) or not 0 <= i < len(vols) for i in which) \
-            or len(set(which)) != len(which):
+    if not which or any(not _is_int(i) or not 0 <= i < len(vols) for i in which) or len(set(which)) != len(which):
         raise ValueError(f"volumes must name some of the {len(vols)} volume arguments once each, got {which!r}")
-    B = vols[0].shape[0]
-    if any(v.dim() < 4 or v.shape[0] != B for v in vols):
-        raise ValueError("volumes must be (B, ..., D, H, W) with one batch size")
     size = tuple(int(s) for s in vols[which[0]].shape[-3:])
     if any(tuple(vols[i].shape[-3:]) != size or vols[i].numel() != B * size[0] * size[1] * size[2] for i in which):
         raise ValueError("the occluded volumes must be one-channel volumes of one spatial shape")
@@ -174,85 +104,24 @@ def _run(model, volumes, patch, stride, atlas, fill, score, target, output, whic
         if nW < 1:
             raise ValueError("atlas has no label above 0: nothing to occlude")
         atlas = atlas.detach().to(device=vols[which[0]].device, dtype=torch.int32).contiguous()
-    fills = {}
-    for i in which:
-        v = vols[i]
-        if isinstance(fill, str):
-            if fill != "mean":
-                raise ValueError(f"fill must be a float, \"mean\" or a tensor ({B},), got {fill!r}")
-            fills[i] = v.reshape(B, -1).mean(1)
-        elif torch.is_tensor(fill):
-            if tuple(fill.shape) != (B,):
-                raise ValueError(f"a fill tensor must be ({B},), got {tuple(fill.shape)}")
-            fills[i] = fill.detach().to(device=v.device, dtype=v.dtype).contiguous()
-        elif isinstance(fill, (int, float)) and not isinstance(fill, bool):
-            fills[i] = torch.full((B,), float(fill), device=v.device, dtype=v.dtype)
-        else:
-            raise ValueError(f"fill must be a float, \"mean\" or a tensor ({B},), got {fill!r}")
+    fills = {i: _fill(fill, vols[i], B) for i in which}
 
     def occlude(i, j0, K, out):
-        v = vols[i]
-        if torch_only:                                                  # clone and slice assignment, as a user writes it
-            jobs = torch.arange(j0, j0 + K, device=v.device)
-            x = v.index_select(0, jobs // nW).clone()
-            labels = None if atlas is None else atlas.to(v.device)
-            for k in range(K):
-                b, w = divmod(j0 + k, nW)
-                region = ops.occlusion_window(size, patch, stride, w) if atlas is None else (labels == w + 1,)
-                x[k][(..., *region)] = fills[i][b]
-            return x
         if atlas is None:
-            return ops.occlude_windows(v, fills[i], patch, stride, j0, K, out=out)
-        return ops.occlude_labels(v, atlas, fills[i], nW, j0, K, out=out)
+            return (ops.occlude_windows_torch if torch_only else ops.occlude_windows)(vols[i], fills[i], patch, stride, j0, K, out=out)
+        return (ops.occlude_labels_torch if torch_only else ops.occlude_labels)(vols[i], atlas, fills[i], nW, j0, K, out=out)
 
-    # the library launches on the CURRENT device's current stream: make the volumes' device current for the duration
-    guard = torch.cuda.device(vols[0].device) if vols[0].is_cuda else contextlib.nullcontext()
-    with torch.no_grad(), guard:
-        logits, encoders = _baseline(model, vols, output, reuse and not torch_only)
-        target = _resolve_target(target, logits)
-        base = _score(logits, target, score)
-        sides = []
-        if logits.is_cuda:
-            # the two-encoder models run one encoder on a side stream: order it ahead of the reads of its kept output
-            from . import mymodel
-            cur = torch.cuda.current_stream(logits.device)
-            sides = mymodel.backward_streams(logits.device)
-            for s in sides:
-                cur.wait_stream(s)
-            for encs in encoders.values():
-                for _enc, out in encs:
-                    out.record_stream(cur)
+    with torch.no_grad(), _on(vols[0]):
+        run = _Pass(model, vols, score, target, output, chunk, reuse)
         drops, maps = {}, {}
         for occluded in ([which] if joint else [(i,) for i in which]):
-            kept = [e for i, encs in encoders.items() if i not in occluded for e in encs]
-            replayed = {i for i in encoders if i not in occluded}
             # the chunk buffers of the kernel path, allocated once per pass (the torch ops allocate as they go)
-            bufs = {i: torch.empty((min(chunk, B * nW),) + tuple(vols[i].shape[1:]), device=vols[i].device, dtype=vols[i].dtype)
-                    for i in occluded if not torch_only and ops.occlusion_ok(vols[i])}
-            d = torch.empty((B * nW,), device=logits.device, dtype=logits.dtype)
-            with _Replay(kept) as replay:
-                for j0 in range(0, B * nW, chunk):
-                    K = min(chunk, B * nW - j0)
-                    rows = torch.arange(j0, j0 + K, device=logits.device) // nW
-                    batch = []
-                    for i, v in enumerate(vols):
-                        if i in occluded:
-                            batch.append(occlude(i, j0, K, bufs[i][:K] if i in bufs else None))
-                        elif i in replayed:
-                            batch.append(v[:1].expand(K, *v.shape[1:]))        # not read: its encoder replays
-                        else:
-                            batch.append(v.index_select(0, rows.to(v.device)))
-                    replay.set(rows)
-                    out = _logits(model, batch, output)
-                    d[j0:j0 + K] = base.index_select(0, rows) - _score(out, target.index_select(0, rows), score)
-            for i in bufs:
-                for s in sides:
-                    bufs[i].record_stream(s)
-            d = d.view(B, nW)
+            buffered = [i for i in occluded if not torch_only and ops.occlusion_ok(vols[i])]
+            d = run.base.view(B, 1) - run.scores(occluded, nW, occlude, buffered).view(B, nW)
             vmap = (ops.occlusion_volume_torch if torch_only else ops.occlusion_volume)(d, size, patch, stride, labels=atlas)
             for i in (occluded[:1] if joint else occluded):
                 drops[i], maps[i] = d, vmap
-    return Occlusion(logits, target, base, grid, patch, stride, which, bool(joint), size, drops, maps)
+    return Occlusion(run.logits, run.target, run.base, grid, patch, stride, which, bool(joint), size, drops, maps)
 
 
 def occlusion_sensitivity(model, *vols, patch=12, stride=None, atlas=None, fill=0.0, score="logit", target=None, output=0,

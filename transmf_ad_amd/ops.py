@@ -7,6 +7,7 @@ fp32, contiguous, on a HIP device; activations are channels-last (B, D, H, W, C)
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -1307,10 +1308,28 @@ def fusion_attn_maps(mri_tok, pet_tok, cfg, params, want_probs):
 CAM_METHODS = {"gradcam": _lib.CAM_GRAD, "hirescam": _lib.CAM_HIRES}
 
 
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _int(v, msg, lo, hi=None):
+    """v if it is an int (no bool) in lo..hi (hi None: no upper end); ValueError(f"{msg}, got {v!r}") otherwise."""
+    if not _is_int(v) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{msg}, got {v!r}")
+    return v
+
+
+def _kernel_takes(*pairs, contiguous=True):
+    """The one device test of the explanation kernels.  pairs: (tensor, the dtype its entry reads - or a tuple of dtypes); all on
+    one HIP device, each of its dtype, contiguous (unless `contiguous` is off) and not empty."""
+    dev = pairs[0][0].device
+    return all(t.is_cuda and t.device == dev and t.dtype in (d if isinstance(d, tuple) else (d,))
+               and (t.is_contiguous() or not contiguous) and t.numel() > 0 for t, d in pairs)
+
+
 def cam_ok(act, grad):
     """tmf_cam takes this pair: float32 tensors on one HIP device, a channel count tmf_cam_ok accepts, at least one voxel."""
-    return (act.is_cuda and grad.is_cuda and act.device == grad.device and act.dtype == _f32 and grad.dtype == _f32
-            and act.numel() > 0 and bool(_lib.query("tmf_cam_ok", int(act.shape[-1]))))
+    return _kernel_takes((act, _f32), (grad, _f32), contiguous=False) and bool(_lib.query("tmf_cam_ok", int(act.shape[-1])))
 
 
 def cam(act, grad, method="gradcam", relu=True, normalize=True):
@@ -1349,7 +1368,7 @@ def occlusion_grid(size, patch, stride):
     if not (len(size) == len(patch) == len(stride) == 3):
         raise ValueError(f"size, patch and stride are three numbers each, got {size}, {patch}, {stride}")
     for S, p, s in zip(size, patch, stride):
-        if any(not isinstance(v, int) or isinstance(v, bool) for v in (S, p, s)) or S < 1 or p < 1:
+        if not all(_is_int(v) for v in (S, p, s)) or S < 1 or p < 1:
             raise ValueError(f"extents and patches are positive integers, got size {size}, patch {patch}, stride {stride}")
         if not 1 <= s <= p:
             raise ValueError(f"stride {stride} must lie in 1..patch {patch} on every axis: voxels would lie in no window")
@@ -1365,12 +1384,11 @@ def occlusion_window(size, patch, stride, w):
 
 def occlusion_ok(*tensors):
     """The occlusion kernels take these: contiguous float32 (int32 for labels) tensors on one HIP device, none empty."""
-    dev = tensors[0].device
-    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32) and t.is_contiguous() and t.numel() > 0
-               for t in tensors)
+    return _kernel_takes(*((t, (_f32, torch.int32)) for t in tensors))
 
 
-def _occlusion_out(vol, K, out):
+def _job_buffer(vol, K, out):
+    """The (K, ...) buffer a chunk of K jobs on the rows of vol (B, ...) is written to: `out` if it fits, a new one for None."""
     shape = (K,) + tuple(vol.shape[1:])
     if out is None:
         return torch.empty(shape, device=vol.device, dtype=vol.dtype)
@@ -1379,28 +1397,26 @@ def _occlusion_out(vol, K, out):
     return out
 
 
-def _occlusion_jobs(B, nW, j0, K):
+def _job_range(B, nW, j0, K):
+    """Jobs j0 .. j0+K-1 lie among the B * nW jobs, or ValueError."""
     if not (K >= 1 and j0 >= 0 and j0 + K <= B * nW):
         raise ValueError(f"jobs {j0} .. {j0 + K - 1} of {B * nW}")
 
 
-def occlude_windows(vol, fill, patch, stride, j0, K, out=None):
-    """out[k] = vol[(j0+k) // nW] with window (j0+k) % nW of its last three axes set to fill[(j0+k) // nW]: vol (B, ..., D, H, W),
-    fill (B,) -> (K, ..., D, H, W), the bits of clone() plus slice assignment.  Contiguous float32 HIP tensors: ONE launch
-    (tmf_occlude_windows); anything else: those torch ops.  out: a buffer to write into (contiguous for the kernel)."""
+def _occlude_args(vol, fill, nW, j0, K, out, labels=None):
+    """The checks of occlude_windows and occlude_labels (nW = R) -> the (K, ...) buffer to write."""
     B, size = vol.shape[0], tuple(vol.shape[-3:])
-    grid = occlusion_grid(size, patch, stride)
-    nW = grid[0] * grid[1] * grid[2]
-    _occlusion_jobs(B, nW, j0, K)
-    out = _occlusion_out(vol, K, out)
+    if labels is not None and (tuple(labels.shape) != size or labels.dtype.is_floating_point or nW < 1):
+        raise ValueError(f"labels must be integers of shape {size} and R >= 1, got {tuple(labels.shape)} {labels.dtype}, R = {nW}")
+    _job_range(B, nW, j0, K)
+    out = _job_buffer(vol, K, out)
     if tuple(fill.shape) != (B,):
         raise ValueError(f"fill must be ({B},), got {tuple(fill.shape)}")
-    if occlusion_ok(vol, fill, out) and vol.dtype == _f32 and fill.dtype == _f32 \
-            and vol.numel() == B * size[0] * size[1] * size[2]:             # one channel: (B, 1, D, H, W) or (B, D, H, W)
-        _chk(vol, "vol")
-        _lib.call("tmf_occlude_windows", vol.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *size, *patch, *stride, j0, K,
-                  _stream())
-        return out
+    return out
+
+
+def _occlude_windows_rows(vol, fill, patch, stride, nW, j0, K, out):
+    size = tuple(vol.shape[-3:])
     jobs = torch.arange(j0, j0 + K, device=vol.device)
     out.copy_(vol.index_select(0, jobs // nW))
     for k in range(K):
@@ -1409,25 +1425,53 @@ def occlude_windows(vol, fill, patch, stride, j0, K, out=None):
     return out
 
 
-def occlude_labels(vol, labels, fill, R, j0, K, out=None):
-    """occlude_windows with regions: job (j0+k) = b*R + (r-1) sets the voxels of sample b whose label (labels (D, H, W),
-    integers) is r to fill[b]; label 0 and labels outside 0..R occlude nothing.  Kernel: tmf_occlude_labels (int32 labels)."""
+def occlude_windows_torch(vol, fill, patch, stride, j0, K, out=None):
+    """occlude_windows in plain torch ops on whatever device and dtype vol has: the samples' rows copied, then one slice
+    assignment of fill[b], cast to vol's dtype, per job."""
+    nW = math.prod(occlusion_grid(tuple(vol.shape[-3:]), patch, stride))
+    return _occlude_windows_rows(vol, fill, patch, stride, nW, j0, K, _occlude_args(vol, fill, nW, j0, K, out))
+
+
+def occlude_windows(vol, fill, patch, stride, j0, K, out=None):
+    """out[k] = vol[(j0+k) // nW] with window (j0+k) % nW of its last three axes set to fill[(j0+k) // nW]: vol (B, ..., D, H, W),
+    fill (B,) -> (K, ..., D, H, W), the bits of clone() plus slice assignment.  Contiguous float32 HIP tensors: ONE launch
+    (tmf_occlude_windows); anything else: occlude_windows_torch.  out: a buffer to write into (contiguous for the kernel)."""
     B, size = vol.shape[0], tuple(vol.shape[-3:])
-    if tuple(labels.shape) != size or labels.dtype.is_floating_point or R < 1:
-        raise ValueError(f"labels must be integers of shape {size} and R >= 1, got {tuple(labels.shape)} {labels.dtype}, R = {R}")
-    _occlusion_jobs(B, R, j0, K)
-    out = _occlusion_out(vol, K, out)
-    if tuple(fill.shape) != (B,):
-        raise ValueError(f"fill must be ({B},), got {tuple(fill.shape)}")
-    if occlusion_ok(vol, fill, out, labels) and vol.dtype == _f32 and fill.dtype == _f32 and labels.dtype == torch.int32 \
-            and vol.numel() == B * labels.numel():
-        _chk(vol, "vol")
-        _lib.call("tmf_occlude_labels", vol.data_ptr(), labels.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *size, R, j0, K,
-                  _stream())
-        return out
+    nW = math.prod(occlusion_grid(size, patch, stride))
+    out = _occlude_args(vol, fill, nW, j0, K, out)
+    if not (_kernel_takes((vol, _f32), (fill, _f32), (out, _f32))
+            and vol.numel() == B * size[0] * size[1] * size[2]):           # one channel: (B, 1, D, H, W) or (B, D, H, W)
+        return _occlude_windows_rows(vol, fill, patch, stride, nW, j0, K, out)
+    _chk(vol, "vol")
+    _lib.call("tmf_occlude_windows", vol.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *size, *patch, *stride, j0, K, _stream())
+    return out
+
+
+def _occlude_labels_rows(vol, labels, fill, R, j0, K, out):
+    labels = labels.to(vol.device)
     for k in range(K):
         b, r = divmod(j0 + k, R)
-        out[k] = torch.where(labels.to(vol.device) == r + 1, fill[b], vol[b])
+        out[k] = torch.where(labels == r + 1, fill[b], vol[b])
+    return out
+
+
+def occlude_labels_torch(vol, labels, fill, R, j0, K, out=None):
+    """occlude_labels in plain torch ops on whatever device and dtype vol has: one torch.where per job, fill[b] cast to vol's
+    dtype."""
+    return _occlude_labels_rows(vol, labels, fill, R, j0, K, _occlude_args(vol, fill, R, j0, K, out, labels))
+
+
+def occlude_labels(vol, labels, fill, R, j0, K, out=None):
+    """occlude_windows with regions: job (j0+k) = b*R + (r-1) sets the voxels of sample b whose label (labels (D, H, W),
+    integers) is r to fill[b]; label 0 and labels outside 0..R occlude nothing.  Kernel: tmf_occlude_labels (int32 labels);
+    anything else: occlude_labels_torch."""
+    out = _occlude_args(vol, fill, R, j0, K, out, labels)
+    B = vol.shape[0]
+    if not (_kernel_takes((vol, _f32), (fill, _f32), (out, _f32), (labels, torch.int32)) and vol.numel() == B * labels.numel()):
+        return _occlude_labels_rows(vol, labels, fill, R, j0, K, out)
+    _chk(vol, "vol")
+    _lib.call("tmf_occlude_labels", vol.data_ptr(), labels.data_ptr(), fill.data_ptr(), out.data_ptr(), B, *labels.shape, R, j0, K,
+              _stream())
     return out
 
 
@@ -1460,7 +1504,7 @@ def occlusion_volume(drops, size, patch=None, stride=None, labels=None):
         grid = occlusion_grid(size, patch, stride)
         if nW != grid[0] * grid[1] * grid[2]:
             raise ValueError(f"drops {tuple(drops.shape)} do not belong to the {grid} windows of {size}")
-        if occlusion_ok(drops) and drops.dtype == _f32:
+        if _kernel_takes((drops, _f32)):
             _chk(drops, "drops")
             vmap = torch.empty((B,) + size, device=drops.device, dtype=_f32)
             _lib.call("tmf_occlusion_volume", drops.data_ptr(), vmap.data_ptr(), B, *size, *patch, *stride, _stream())
@@ -1468,7 +1512,7 @@ def occlusion_volume(drops, size, patch=None, stride=None, labels=None):
         return occlusion_volume_torch(drops, size, patch, stride)
     if tuple(labels.shape) != size or labels.dtype.is_floating_point:
         raise ValueError(f"labels must be integers of shape {size}, got {tuple(labels.shape)} {labels.dtype}")
-    if occlusion_ok(drops, labels) and drops.dtype == _f32 and labels.dtype == torch.int32:
+    if _kernel_takes((drops, _f32), (labels, torch.int32)):
         _chk(drops, "drops")
         vmap = torch.empty((B,) + size, device=drops.device, dtype=_f32)
         _lib.call("tmf_occlusion_volume_labels", drops.data_ptr(), labels.data_ptr(), vmap.data_ptr(), B, *size, nW, _stream())
@@ -1486,15 +1530,14 @@ RANK_MODES = {"deletion": _lib.RANK_DELETION, "insertion": _lib.RANK_INSERTION}
 def rank_counts(V, steps):
     """[n_1 .. n_steps], n_k = ceil(k*V / steps): the number of voxels step k removes at least.  Non-decreasing, each in
     1..V, n_steps = V; repeated where V < steps."""
-    if any(not isinstance(v, int) or isinstance(v, bool) for v in (V, steps)) or V < 1 or not 1 <= steps <= _lib.RANK_MAX_STEPS:
+    if not (_is_int(V) and _is_int(steps)) or V < 1 or not 1 <= steps <= _lib.RANK_MAX_STEPS:
         raise ValueError(f"V must be a positive integer and steps one in 1..{_lib.RANK_MAX_STEPS}, got V = {V!r}, steps = {steps!r}")
     return [-(-k * V // steps) for k in range(1, steps + 1)]
 
 
 def faithfulness_ok(*tensors):
     """The kernels of csrc/faithfulness.hip take these: contiguous float32 tensors on one HIP device, none empty."""
-    dev = tensors[0].device
-    return all(t.is_cuda and t.device == dev and t.dtype == _f32 and t.is_contiguous() and t.numel() > 0 for t in tensors)
+    return _kernel_takes(*((t, _f32) for t in tensors))
 
 
 def _rank_counts_checked(V, counts):
@@ -1505,65 +1548,93 @@ def _rank_counts_checked(V, counts):
     return counts
 
 
-def rank_thresholds(attr, counts):
-    """attr (B, ...) with V elements per sample, counts [S] (rank_counts) -> (thr (B, S) of attr's dtype, removed (B, S) int32):
-    thr[b, k] = the counts[k]-th largest a = attr + 0.0 of sample b, removed[b, k] = the number of its voxels with a >= thr[b, k]
-    (ties go together).  Contiguous float32 HIP tensors: a radix select without a sort (tmf_rank_thresholds); anything else:
-    sort(descending=True), a gather and >=."""
+def _rank_args(attr, counts):
     B = attr.shape[0]
-    a = attr.reshape(B, -1)
-    V = a.shape[1]
+    V = attr.numel() // B if B else 0
     if B < 1 or V < 1:
         raise ValueError(f"attr must hold samples with voxels, got {tuple(attr.shape)}")
-    counts = _rank_counts_checked(V, counts)
+    return B, V, _rank_counts_checked(V, counts)
+
+
+def _rank_thresholds_sorted(attr, B, counts):
     S = len(counts)
-    if faithfulness_ok(attr):
-        _chk(attr, "attr")
-        thr = torch.empty((B, S), device=attr.device, dtype=_f32)
-        removed = torch.empty((B, S), device=attr.device, dtype=torch.int32)
-        nws = _lib.query("tmf_rank_workspace_bytes", B, V, S)
-        ws = torch.empty((nws,), device=attr.device, dtype=torch.uint8)        # the entry zeroes it
-        _lib.call("tmf_rank_thresholds", attr.data_ptr(), (ctypes.c_int * S)(*counts), thr.data_ptr(), removed.data_ptr(),
-                  ws.data_ptr(), nws, B, V, S, _stream())
-        return thr, removed
-    a = a + 0.0
+    a = attr.reshape(B, -1) + 0.0
     srt = a.sort(1, descending=True).values
     thr = srt.gather(1, torch.tensor(counts, device=a.device).view(1, S).expand(B, S) - 1)
     removed = torch.stack([(a >= thr[:, k:k + 1]).sum(1) for k in range(S)], 1).to(torch.int32)
     return thr, removed
 
 
-def mask_by_rank(vol, attr, thr, fill, mode, j0, K, base=None, out=None):
-    """Job j0 + k = b*(S+1) + s, s in 0..S: m = (s > 0) & (attr[b] + 0.0 >= thr[b, s-1]); out[k] = where(m, f, vol[b]) for mode
-    "deletion", where(m, vol[b], f) for "insertion", f = base[b] (a tensor of vol's shape) where given, else fill[b] (fill (B,)).
-    vol, attr (B, ...) with the same number of elements, thr (B, S) -> (K, ...) of vol's shape.  Contiguous float32 HIP
-    tensors: ONE launch (tmf_mask_by_rank); anything else: torch.where.  out: a buffer to write into."""
+def rank_thresholds_torch(attr, counts):
+    """rank_thresholds in plain torch ops on whatever device and dtype attr has: sort(descending=True), a gather and >=."""
+    B, _V, counts = _rank_args(attr, counts)
+    return _rank_thresholds_sorted(attr, B, counts)
+
+
+def rank_thresholds(attr, counts):
+    """attr (B, ...) with V elements per sample, counts [S] (rank_counts) -> (thr (B, S) of attr's dtype, removed (B, S) int32):
+    thr[b, k] = the counts[k]-th largest a = attr + 0.0 of sample b, removed[b, k] = the number of its voxels with a >= thr[b, k]
+    (ties go together).  Contiguous float32 HIP tensors: a radix select without a sort (tmf_rank_thresholds); anything else:
+    rank_thresholds_torch."""
+    B, V, counts = _rank_args(attr, counts)
+    if not _kernel_takes((attr, _f32)):
+        return _rank_thresholds_sorted(attr, B, counts)
+    _chk(attr, "attr")
+    S = len(counts)
+    thr = torch.empty((B, S), device=attr.device, dtype=_f32)
+    removed = torch.empty((B, S), device=attr.device, dtype=torch.int32)
+    nws = _lib.query("tmf_rank_workspace_bytes", B, V, S)
+    ws = torch.empty((nws,), device=attr.device, dtype=torch.uint8)            # the entry zeroes it
+    _lib.call("tmf_rank_thresholds", attr.data_ptr(), (ctypes.c_int * S)(*counts), thr.data_ptr(), removed.data_ptr(),
+              ws.data_ptr(), nws, B, V, S, _stream())
+    return thr, removed
+
+
+def _mask_args(vol, attr, thr, fill, mode, j0, K, base, out):
     if mode not in RANK_MODES:
         raise ValueError(f"mode must be one of {tuple(RANK_MODES)}, got {mode!r}")
     B = vol.shape[0]
     if thr.dim() != 2 or thr.shape[0] != B or not 1 <= thr.shape[1] <= _lib.RANK_MAX_STEPS:
         raise ValueError(f"thr must be ({B}, S) with S in 1..{_lib.RANK_MAX_STEPS}, got {tuple(thr.shape)}")
-    S = thr.shape[1]
     if attr.shape[0] != B or attr.numel() != vol.numel():
         raise ValueError(f"attr {tuple(attr.shape)} does not hold one value per voxel of vol {tuple(vol.shape)}")
     if base is not None and tuple(base.shape) != tuple(vol.shape):
         raise ValueError(f"base must have vol's shape {tuple(vol.shape)}, got {tuple(base.shape)}")
     if base is None and (fill is None or tuple(fill.shape) != (B,)):
         raise ValueError(f"fill must be ({B},), got {None if fill is None else tuple(fill.shape)}")
-    _occlusion_jobs(B, S + 1, j0, K)
-    out = _occlusion_out(vol, K, out)
-    f = base if base is not None else fill
-    if faithfulness_ok(vol, attr, thr, f, out):
-        _chk(vol, "vol")
-        _lib.call("tmf_mask_by_rank", vol.data_ptr(), attr.data_ptr(), thr.data_ptr(), _ptr(None if base is not None else fill),
-                  _ptr(base), out.data_ptr(), B, vol.numel() // B, S, RANK_MODES[mode], j0, K, _stream())
-        return out
+    _job_range(B, thr.shape[1] + 1, j0, K)
+    return _job_buffer(vol, K, out)
+
+
+def _mask_rows(vol, attr, thr, fill, mode, j0, K, base, out):
+    S = thr.shape[1]
     a = attr.reshape(vol.shape) + 0.0
     for k in range(K):
         b, s = divmod(j0 + k, S + 1)
         m = a[b] >= thr[b, s - 1] if s else torch.zeros_like(a[b], dtype=torch.bool)
         g = base[b] if base is not None else fill[b].to(vol.dtype)
         out[k] = torch.where(m, g, vol[b]) if mode == "deletion" else torch.where(m, vol[b], g)
+    return out
+
+
+def mask_by_rank_torch(vol, attr, thr, fill, mode, j0, K, base=None, out=None):
+    """mask_by_rank in plain torch ops on whatever device and dtype the tensors have: >= and one torch.where per job, fill[b]
+    cast to vol's dtype."""
+    return _mask_rows(vol, attr, thr, fill, mode, j0, K, base, _mask_args(vol, attr, thr, fill, mode, j0, K, base, out))
+
+
+def mask_by_rank(vol, attr, thr, fill, mode, j0, K, base=None, out=None):
+    """Job j0 + k = b*(S+1) + s, s in 0..S: m = (s > 0) & (attr[b] + 0.0 >= thr[b, s-1]); out[k] = where(m, f, vol[b]) for mode
+    "deletion", where(m, vol[b], f) for "insertion", f = base[b] (a tensor of vol's shape) where given, else fill[b] (fill (B,)).
+    vol, attr (B, ...) with the same number of elements, thr (B, S) -> (K, ...) of vol's shape.  Contiguous float32 HIP
+    tensors: ONE launch (tmf_mask_by_rank); anything else: mask_by_rank_torch.  out: a buffer to write into."""
+    out = _mask_args(vol, attr, thr, fill, mode, j0, K, base, out)
+    if not faithfulness_ok(vol, attr, thr, base if base is not None else fill, out):
+        return _mask_rows(vol, attr, thr, fill, mode, j0, K, base, out)
+    _chk(vol, "vol")
+    B = vol.shape[0]
+    _lib.call("tmf_mask_by_rank", vol.data_ptr(), attr.data_ptr(), thr.data_ptr(), _ptr(None if base is not None else fill),
+              _ptr(base), out.data_ptr(), B, vol.numel() // B, thr.shape[1], RANK_MODES[mode], j0, K, _stream())
     return out
 
 
@@ -1579,9 +1650,7 @@ REGION_FIELDS = ("count", "sum", "abs_sum", "pos_sum", "max", "argmax")
 def region_ok(*tensors):
     """The kernels of csrc/region_stats.hip take these: contiguous float32 (int32 labels, int64 classes, float64 state) tensors
     on one HIP device, none empty."""
-    dev = tensors[0].device
-    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32, torch.int64, torch.float64) and t.is_contiguous()
-               and t.numel() > 0 for t in tensors)
+    return _kernel_takes(*((t, (_f32, torch.int32, torch.int64, torch.float64)) for t in tensors))
 
 
 def _region_args(a, labels, R):
@@ -1589,8 +1658,7 @@ def _region_args(a, labels, R):
         raise ValueError(f"a must be a floating-point tensor (B, V) with samples and voxels, got {tuple(a.shape)} {a.dtype}")
     if labels.dim() != 1 or labels.shape[0] != a.shape[1] or labels.dtype.is_floating_point or labels.dtype == torch.bool:
         raise ValueError(f"labels must be integers ({a.shape[1]},), got {tuple(labels.shape)} {labels.dtype}")
-    if not isinstance(R, int) or isinstance(R, bool) or R < 1:
-        raise ValueError(f"R must be an integer >= 1, got {R!r}")
+    _int(R, "R must be an integer >= 1", 1)
 
 
 def region_stats_torch(a, labels, R):
@@ -1620,7 +1688,7 @@ def region_stats(a, labels, R):
     Contiguous float32 HIP `a`, int32 labels and R <= REGION_MAX: tmf_region_stats (integer sums: the same bits on every call,
     no host read); anything else: region_stats_torch."""
     _region_args(a, labels, R)
-    if not (R <= REGION_MAX and region_ok(a, labels) and a.dtype == _f32 and labels.dtype == torch.int32):
+    if not (R <= REGION_MAX and _kernel_takes((a, _f32), (labels, torch.int32))):
         return region_stats_torch(a, labels, R)
     _chk(a, "a")
     B, V = a.shape
@@ -1648,8 +1716,8 @@ def region_group_update(state, values, cls):
         raise ValueError(f"values must be (B, {R + 1}) or (B, {R}) and cls integers (B,), got {tuple(values.shape)} and "
                          f"{tuple(cls.shape)} {cls.dtype}")
     B, first = values.shape[0], R + 1 - values.shape[1]
-    if C <= REGION_MAX_CLASSES and R <= REGION_MAX and B <= 65536 and region_ok(state, values, cls) and values.dtype == _f32 \
-            and cls.dtype == torch.int64:
+    if C <= REGION_MAX_CLASSES and R <= REGION_MAX and B <= 65536 \
+            and _kernel_takes((state, torch.float64), (values, _f32), (cls, torch.int64)):
         _chk(values, "values")
         _lib.call("tmf_region_group_update", values.data_ptr(), cls.data_ptr(), state.data_ptr(), B, R, C, first, _stream())
         return state
@@ -1672,9 +1740,7 @@ CLUSTER_CONNECTIVITIES = (6, 18, 26)
 
 def cluster_ok(*tensors):
     """The kernels of csrc/clusters.hip take these: contiguous float32 (int32 labels) tensors on one HIP device, none empty."""
-    dev = tensors[0].device
-    return all(t.is_cuda and t.device == dev and t.dtype in (_f32, torch.int32) and t.is_contiguous() and t.numel() > 0
-               for t in tensors)
+    return _kernel_takes(*((t, (_f32, torch.int32)) for t in tensors))
 
 
 def _cluster_score(a, mode):
@@ -1690,8 +1756,7 @@ def _cluster_label_args(a, thr, mode, connectivity, min_size):
         raise ValueError(f"mode must be one of {tuple(CLUSTER_MODES)}, got {mode!r}")
     if connectivity not in CLUSTER_CONNECTIVITIES:
         raise ValueError(f"connectivity must be one of {CLUSTER_CONNECTIVITIES}, got {connectivity!r}")
-    if not isinstance(min_size, int) or isinstance(min_size, bool) or min_size < 1:
-        raise ValueError(f"min_size must be an integer >= 1, got {min_size!r}")
+    _int(min_size, "min_size must be an integer >= 1", 1)
 
 
 def _shifted(x, dim, step, fill):
@@ -1753,7 +1818,7 @@ def cluster_label(a, thr, mode="pos", connectivity=26, min_size=1):
     Contiguous float32 HIP tensors: tmf_cluster_label (eight stream operations whatever the data, no host read); anything else:
     cluster_label_torch."""
     _cluster_label_args(a, thr, mode, connectivity, min_size)
-    if not (cluster_ok(a, thr) and a.dtype == _f32 and thr.dtype == _f32 and a.shape[0] <= 65536):
+    if not (_kernel_takes((a, _f32), (thr, _f32)) and a.shape[0] <= 65536):
         return cluster_label_torch(a, thr, mode, connectivity, min_size)
     _chk(a, "a")
     B, D, H, W = a.shape
@@ -1773,8 +1838,7 @@ def _cluster_table_args(a, labels, mode, K):
         raise ValueError(f"labels must be integers {tuple(a.shape)}, got {tuple(labels.shape)} {labels.dtype}")
     if mode not in CLUSTER_MODES:
         raise ValueError(f"mode must be one of {tuple(CLUSTER_MODES)}, got {mode!r}")
-    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= a[0].numel():
-        raise ValueError(f"K must be an integer in 1..{a[0].numel()} (the voxels of a sample), got {K!r}")
+    _int(K, f"K must be an integer in 1..{a[0].numel()} (the voxels of a sample)", 1, a[0].numel())
 
 
 def cluster_table_torch(a, labels, mode="pos", K=1):
@@ -1816,7 +1880,7 @@ def cluster_table(a, labels, mode="pos", K=1):
     cluster_table_torch."""
     _cluster_table_args(a, labels, mode, K)
     B = a.shape[0]
-    if not (cluster_ok(a, labels) and a.dtype == _f32 and labels.dtype == torch.int32 and B <= 65536 and B * K < 1 << 31):
+    if not (_kernel_takes((a, _f32), (labels, torch.int32)) and B <= 65536 and B * K < 1 << 31):
         return cluster_table_torch(a, labels, mode, K)
     _chk(a, "a")
     size, arg = (torch.empty((B, K), device=a.device, dtype=torch.int32) for _ in range(2))

@@ -24,12 +24,12 @@ Contiguous float32 maps on a HIP device with R <= ops.REGION_MAX take the kernel
 csrc/region_stats.hip: four stream operations, no host synchronisation); every other tensor - another dtype or layout, the
 CPU - takes region_stats_torch, the same function in bincount, index_add_ and scatter_reduce.  region_stats refuses more than
 ops.REGION_MAX regions; region_stats_torch, called directly, has no limit."""
-import contextlib
 import math
 
 import torch
 
 from . import ops
+from ._explain import _attribution, _int, _on, _peak_voxel
 
 __all__ = ["region_stats", "region_stats_torch", "RegionStats", "RegionAccumulator"]
 
@@ -61,18 +61,11 @@ class RegionStats:
 
     def peak_voxel(self, r):
         """(B, 3) int64: the (d, h, w) of bin r's argmax, (-1, -1, -1) where the bin is empty."""
-        if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r <= self.R:
-            raise ValueError(f"r must be a bin in 0..{self.R}, got {r!r}")
-        i = self.argmax[:, r].long()
-        _D, H, W = self.size
-        zyx = torch.stack([i // (H * W), i // W % H, i % W], 1)
-        return torch.where((i >= 0).view(-1, 1), zyx, torch.full_like(zyx, -1))
+        return _peak_voxel(self.argmax[:, _int(r, f"r must be a bin in 0..{self.R}", 0, self.R)], self.size)
 
     def top(self, k, by="abs"):
         """(indices (B, k) int64 in 1..R, values (B, k)): the k regions with the largest share(by), the largest first."""
-        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= self.R:
-            raise ValueError(f"k must lie in 1..{self.R}, got {k!r}")
-        v, i = self.share(by)[:, 1:].topk(k, dim=1)
+        v, i = self.share(by)[:, 1:].topk(_int(k, f"k must lie in 1..{self.R}", 1, self.R), dim=1)
         return i + 1, v
 
     def table(self, names=None):
@@ -95,24 +88,19 @@ class RegionStats:
 
 
 def _run(attribution, atlas, R, torch_only):
-    if not torch.is_tensor(attribution) or not attribution.dtype.is_floating_point or attribution.dim() not in (4, 5) \
-            or (attribution.dim() == 5 and attribution.shape[1] != 1) or attribution.numel() == 0:
-        raise ValueError("attribution must be a floating-point tensor (B, D, H, W) or (B, 1, D, H, W) with voxels, got "
-                         f"{tuple(attribution.shape) if torch.is_tensor(attribution) else attribution!r}")
-    size = tuple(int(s) for s in attribution.shape[-3:])
+    a = _attribution(attribution)
+    size = tuple(int(s) for s in a.shape[-3:])
     if not torch.is_tensor(atlas) or atlas.dtype.is_floating_point or atlas.dtype == torch.bool or tuple(atlas.shape) != size:
         raise ValueError(f"atlas must be an integer label volume of shape {size}")
     if R is None:
         R = int(atlas.max())                                           # a host read; pass R to avoid it
-    if not isinstance(R, int) or isinstance(R, bool) or R < 1:
-        raise ValueError(f"R must be an integer >= 1 (the atlas needs a label above 0), got {R!r}")
+    _int(R, "R must be an integer >= 1 (the atlas needs a label above 0)", 1)
     if not torch_only and R > ops.REGION_MAX:
         raise ValueError(f"R = {R} is above the limit of {ops.REGION_MAX} regions; region_stats_torch has none")
-    a = attribution.detach()
     B = a.shape[0]
     # moved and converted once: contiguous int32 on the map's device
     lab = atlas.detach().to(device=a.device, dtype=torch.int32).contiguous().view(-1)
-    with torch.no_grad(), (torch.cuda.device(a.device) if a.is_cuda else contextlib.nullcontext()):
+    with torch.no_grad(), _on(a):
         if torch_only or not a.is_contiguous():
             out = ops.region_stats_torch(a.reshape(B, -1), lab, R)
         else:
@@ -140,11 +128,8 @@ class RegionAccumulator:
     samples in ascending order, no atomics: two runs give the same bits), anything else by the same sums in torch float64."""
 
     def __init__(self, R, num_classes=2):
-        if not isinstance(R, int) or isinstance(R, bool) or R < 1:
-            raise ValueError(f"R must be an integer >= 1, got {R!r}")
-        if not isinstance(num_classes, int) or isinstance(num_classes, bool) or num_classes < 1:
-            raise ValueError(f"num_classes must be an integer >= 1, got {num_classes!r}")
-        self.R, self.num_classes = R, num_classes
+        self.R = _int(R, "R must be an integer >= 1", 1)
+        self.num_classes = _int(num_classes, "num_classes must be an integer >= 1", 1)
         self._state = None
 
     def reset(self):
@@ -174,7 +159,7 @@ class RegionAccumulator:
         state = self._state_on(values.device)
         values = values.detach()
         cls = labels.to(device=values.device, dtype=torch.int64)
-        with (torch.cuda.device(values.device) if values.is_cuda else contextlib.nullcontext()):
+        with _on(values):
             ops.region_group_update(state, values.contiguous(), cls)
 
     def compute(self):

@@ -15,60 +15,9 @@ integrated_gradients steps of them (plus one without a graph when it resolves ta
 explanation of the deployed network that leaves its buffers alone."""
 import torch
 
+from ._explain import _check, _Frozen, _int, _logits, _resolve_target
+
 __all__ = ["input_gradients", "integrated_gradients"]
-
-
-def _logits(model, volumes, output):
-    out = model(*volumes)
-    if isinstance(out, (tuple, list)):
-        if not isinstance(output, int) or isinstance(output, bool) or not -len(out) <= output < len(out):
-            raise ValueError(f"the model returns {len(out)} outputs, output={output!r} does not exist")
-        out = out[output]
-    elif output != 0:
-        raise ValueError(f"the model returns one tensor, output={output} does not exist")
-    if out.dim() != 2:
-        raise ValueError(f"output {output} of the model is not (batch, classes) logits: shape {tuple(out.shape)}")
-    return out
-
-
-def _resolve_target(target, logits):
-    """-> LongTensor (batch,) on the logits' device; None: each sample's argmax class."""
-    B, K = logits.shape
-    if target is None:
-        return logits.detach().argmax(1)
-    if isinstance(target, int):
-        target = torch.full((B,), target, dtype=torch.long)
-    target = torch.as_tensor(target)
-    if target.dim() != 1 or target.shape[0] != B or target.dtype.is_floating_point:
-        raise ValueError(f"target must be None, an int or {B} class indices, got shape {tuple(target.shape)} {target.dtype}")
-    target = target.to(device=logits.device, dtype=torch.long)
-    if bool(((target < 0) | (target >= K)).any()):
-        raise ValueError(f"target holds a class outside 0..{K - 1}")
-    return target
-
-
-class _Frozen:
-    """requires_grad off on every parameter for the duration (the library then skips every weight gradient), restored on exit."""
-
-    def __init__(self, model, on):
-        self.params = [p for p in model.parameters() if p.requires_grad] if on else []
-
-    def __enter__(self):
-        for p in self.params:
-            p.requires_grad_(False)
-
-    def __exit__(self, *exc):
-        for p in self.params:
-            p.requires_grad_(True)
-        return False
-
-
-def _check(volumes):
-    if not volumes:
-        raise ValueError("at least one volume")
-    for v in volumes:
-        if not (torch.is_tensor(v) and v.dtype.is_floating_point):
-            raise ValueError("volumes must be floating-point tensors")
 
 
 def _grads(model, volumes, target, output):
@@ -100,8 +49,7 @@ def integrated_gradients(model, *volumes, baselines=None, steps=16, target=None,
     resolved ONCE, at the volume itself (one more forward, without a graph).  In train mode each of these forwards updates the
     BatchNorm buffers and consumes Dropout random numbers (see the module docstring)."""
     _check(volumes)
-    if not isinstance(steps, int) or isinstance(steps, bool) or steps < 1:
-        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    _int(steps, "steps must be a positive integer", 1)
     if baselines is None:
         baselines = tuple(torch.zeros_like(v) for v in volumes)
     elif torch.is_tensor(baselines):
