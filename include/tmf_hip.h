@@ -1143,6 +1143,65 @@ int    tmf_cluster_label(const float* a, const float* thr, int* labels, int* n_c
 int    tmf_cluster_table(const float* a, const int* labels, int* size, float* peak, int* argmax, int64_t* coord_sum, int* bbox,
                          int B, int D, int H, int W, int mode, int K, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Gaussian smoothing of volumes and voxel maps (csrc/smooth.hip): the separable 3-D Gaussian filter of
+ * scipy.ndimage.gaussian_filter, optionally normalised inside a mask.  The reference has no such function; this entry replaces
+ * what its user writes with stock ops - F.pad plus three F.conv3d calls with 1-D kernels, whose result depends on the
+ * convolution algorithm the backend picks, or a copy to the host - for a blurred baseline (tmf_mask_by_rank's `base`, the
+ * blurred-input baseline of integrated gradients) and for smoothing an attribution map before tmf_cluster_label / tmf_region_stats.
+ *
+ * a [B][D][H][W] float, W fastest -> out of the same shape, EVERY element written; out must not overlap a.
+ * Taps.  Per axis a sigma in voxels, >= 0, and one truncate > 0.  sigma == 0: the axis is not filtered (r = 0, one tap 1).
+ * Otherwise r = (int)(truncate*sigma + 0.5) and w[i] = exp(-0.5*i*i/sigma^2), i = -r..r, computed in double, divided by their
+ * double sum (tmf_gaussian_taps_f64), then rounded once to float (tmf_gaussian_taps) - scipy's kernel.  r <=
+ * TMF_SMOOTH_MAX_RADIUS; a larger radius is refused with TMF_E_ARG.
+ * Border.  The source index for output o and tap i on an axis of extent n is j = o + i, mapped by mode:
+ *   TMF_SMOOTH_REFLECT   p = j mod 2n (non-negative), source p if p < n, else 2n-1-p: d c b a | a b c d | d c b a (scipy's
+ *                        default "reflect"), valid for any r, including r >= n and n == 1;
+ *   TMF_SMOOTH_CONSTANT  a tap with j outside 0..n-1 contributes 0;
+ *   TMF_SMOOTH_NEAREST   j clamped to 0..n-1.
+ * Result.  The three 1-D filters are applied one after another in fp32 - W, then H, then D -, each output element a chain of
+ * fused multiply-adds from 0.0f in ascending tap order.  The bits are a function of the shape and the arguments alone: two
+ * calls give the same bits, a sample filtered alone gives the bits it has at any batch position, and the 16-byte path gives
+ * the bits of the one-element path.  No atomics, no workgroup waits for another.
+ * Error bound.  The weights are positive and sum to 1 within rounding, each pass is a K = 2r+1 term fp32 dot product.  With
+ * E = the sum over the filtered axes of (2*r_axis + 4) and peak_b = max |a[b]|:
+ *     |out - exact| <= E * 2^-24 * peak_b,
+ * exact = the fp64 filter with the double taps.  A zero map gives exact zeros, a map without negative values no negative output.
+ * Mask (may be NULL).  mask [D][H][W] int32, ONE for all samples (the convention of tmf_region_stats' atlas): a voxel is inside
+ * where mask != 0, so an atlas or a label volume of tmf_cluster_label is a mask as it is.  With m the 0/1 inside indicator:
+ *     out = G(a*m) / G(m) inside, 0 outside,
+ * G the filter above under the chosen border mode - normalised convolution: values outside never enter, the weights are
+ * renormalised near the edge.  Inside, G(m) >= w_d[0]*w_h[0]*w_w[0] > 0.  Bound: (2*E + 2) * 2^-24 * max |a[b]*m|.
+ * All three sigmas 0 is allowed: a copy without a mask, a*m with one.
+ * NaN and +-inf propagate as the arithmetic has it: the values written are then unspecified, but nothing faults.
+ * Passes.  TWO launches whatever the data, no memset, no host synchronisation, no allocation; the taps travel by value in the
+ * kernel arguments (3 x 65 floats: no host-to-device copy).  Launch 1 filters W and H on tiles of one d-plane in LDS, the
+ * border mode applied as the tile and its halo are loaded, and writes the intermediate; launch 2 filters D on slabs of planes
+ * in LDS.  With a mask, launch 1 also writes G_hw(m) - once, by the workgroups of sample 0 - and launch 2 filters it along D
+ * and divides; the mask is read once per launch.  16 bytes per lane where W % 4 == 0 and a, out (and mask) are 16-byte aligned,
+ * one element per lane otherwise.
+ * workspace: tmf_smooth_workspace_bytes(B, D, H, W, masked) bytes = the intermediate, B*D*H*W floats (rounded up to 16 bytes),
+ * plus D*H*W floats (likewise) with a mask; 0 for a shape the entry refuses; 16-byte aligned; the entry need not find it zeroed.
+ *
+ * tmf_gaussian_taps / tmf_gaussian_taps_f64: HOST arrays; write the 2r+1 taps of (sigma, truncate) and return r >= 0, or a
+ * TMF_E_*: TMF_E_ARG for a sigma that is negative or not finite, a truncate that is not a finite number > 0, a radius above the
+ * limit and a capacity below 2r+1.  THE definition of the taps: the entry calls it, and so does the package's stock-torch twin.
+ *
+ * a, out and mask 4-byte aligned, the workspace 16-byte (TMF_E_ALIGN).  Limits (TMF_E_SHAPE / TMF_E_ARG / TMF_E_WORKSPACE,
+ * nothing launched): 1 <= B <= 65536; D, H, W >= 1 with D*H*W < 2^31; mode in 0..2; sigmas finite and >= 0, truncate finite
+ * and > 0, every radius <= TMF_SMOOTH_MAX_RADIUS; out overlapping a (TMF_E_ARG). */
+#define TMF_SMOOTH_REFLECT    0
+#define TMF_SMOOTH_CONSTANT   1
+#define TMF_SMOOTH_NEAREST    2
+#define TMF_SMOOTH_MAX_RADIUS 32
+int    tmf_gaussian_taps(double sigma, double truncate, float* taps, int capacity);
+int    tmf_gaussian_taps_f64(double sigma, double truncate, double* taps, int capacity);
+size_t tmf_smooth_workspace_bytes(int B, int D, int H, int W, int masked);
+int    tmf_gaussian_smooth(const float* a, const int* mask, float* out, double sigma_d, double sigma_h, double sigma_w,
+                           double truncate, int mode, void* workspace, size_t workspace_bytes, int B, int D, int H, int W,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ Semantics (include/tmf_hip.h states the same for the kernels):
     masked voxels are replaced by f, the others keep the volume.  mode "insertion": the masked voxels show the volume, the
     others f.  f = baseline[b, voxel] where `baseline` (a tensor of the volume's shape, e.g. a blurred copy) is given, else
     fill[b]: a float (default 0.0), "mean" (the sample's mean) or a tensor (B,), as in occlusion_sensitivity.
+    baseline="blur": the masked volume smoothed with smooth.BLUR_SIGMA voxels in reflect mode (RISE's insertion baseline),
+    the same tensor as baseline=gaussian_smooth(vol, sigma=BLUR_SIGMA); for another sigma pass that tensor.
   Score.  "prob" (default): the softmax probability of class target_b; "logit": logits[b, target_b].  target as
     saliency.input_gradients (None: the argmax of the UNMASKED logits, resolved once).  base_score is that forward's score.
   AUC.  auc = (s_0/2 + s_1 + .. + s_{S-1} + s_S/2) / S by torch ops; `removed` lets a caller integrate over the true
@@ -41,7 +43,7 @@ faithfulness_curve_torch is the same function on sort(descending=True), a gather
 dtype and any nn.Module (the reference's classes on the CPU in float or double); tmf_replay is not used there."""
 import torch
 
-from . import ops
+from . import ops, smooth
 from ._explain import _attribution, _fill, _int, _on, _pass_arguments, _Pass
 
 __all__ = ["faithfulness_curve", "faithfulness_curve_torch", "Faithfulness", "MODES"]
@@ -73,7 +75,11 @@ def _run(model, volumes, attribution, volume, steps, mode, fill, baseline, score
     if bool(torch.isnan(attr).any()):                                   # the one host read
         raise ValueError("attribution holds NaN: voxels cannot be ranked")
     base_vol = None
-    if baseline is not None:
+    if isinstance(baseline, str):
+        if baseline != "blur":
+            raise ValueError(f"baseline must be a tensor of the volume's shape {tuple(v.shape)} or \"blur\", got {baseline!r}")
+        base_vol = (smooth.gaussian_smooth_torch if torch_only else smooth.gaussian_smooth)(v, sigma=smooth.BLUR_SIGMA).contiguous()
+    elif baseline is not None:
         if not torch.is_tensor(baseline) or tuple(baseline.shape) != tuple(v.shape):
             raise ValueError(f"baseline must be a tensor of the volume's shape {tuple(v.shape)}")
         base_vol = baseline.detach().to(device=v.device, dtype=v.dtype).contiguous()

@@ -1892,6 +1892,143 @@ def cluster_table(a, labels, mode="pos", K=1):
     return size, peak, arg, coord_sum, bbox
 
 
+# --------------------------------------------------------------------------------------
+# Gaussian smoothing (csrc/smooth.hip; include/tmf_hip.h states the taps, the border modes, the mask and the error bound)
+# --------------------------------------------------------------------------------------
+
+SMOOTH_MODES = {"reflect": _lib.SMOOTH_REFLECT, "constant": _lib.SMOOTH_CONSTANT, "nearest": _lib.SMOOTH_NEAREST}
+SMOOTH_MAX_RADIUS = _lib.SMOOTH_MAX_RADIUS
+
+
+_smooth_scratch = (ctypes.c_float * (2 * SMOOTH_MAX_RADIUS + 1))()
+
+
+def smooth_radius(sigma, truncate=4.0):
+    """The radius r = (int)(truncate*sigma + 0.5) as tmf_gaussian_taps has it; ValueError, with the library's message, for what it
+    refuses (a negative or non-finite sigma, a bad truncate, a radius above SMOOTH_MAX_RADIUS)."""
+    try:
+        r = _lib.query("tmf_gaussian_taps", float(sigma), float(truncate), ctypes.addressof(_smooth_scratch), len(_smooth_scratch))
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma and truncate must be numbers, got {sigma!r} and {truncate!r}") from None
+    if r < 0:
+        raise ValueError(_lib.query("tmf_last_error_string").decode())
+    return r
+
+
+def gaussian_taps(sigma, truncate=4.0, dtype=_f32):
+    """The 2r+1 taps of one axis as the library defines them -> a CPU tensor: float32 from tmf_gaussian_taps (what the kernels
+    use), float64 from tmf_gaussian_taps_f64 (the taps before their one rounding).  sigma 0: the one tap 1.  ValueError, with
+    the library's message, for what the entry refuses (a negative or non-finite sigma, a bad truncate, a radius above
+    SMOOTH_MAX_RADIUS)."""
+    if dtype not in (_f32, torch.float64):
+        raise ValueError(f"taps are float32 or float64, got {dtype}")
+    try:
+        sigma, truncate = float(sigma), float(truncate)
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma and truncate must be numbers, got {sigma!r} and {truncate!r}") from None
+    n = 2 * SMOOTH_MAX_RADIUS + 1
+    buf = ((ctypes.c_float if dtype == _f32 else ctypes.c_double) * n)()
+    r = _lib.query("tmf_gaussian_taps" if dtype == _f32 else "tmf_gaussian_taps_f64", sigma, truncate, ctypes.addressof(buf), n)
+    if r < 0:
+        raise ValueError(_lib.query("tmf_last_error_string").decode())
+    return torch.tensor(buf[:2 * r + 1], dtype=dtype)
+
+
+def _smooth_args(a, sigma3, truncate, mode, mask):
+    if a.dim() != 4 or a.numel() == 0 or not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor (B, D, H, W) with voxels, got {tuple(a.shape)} {a.dtype}")
+    if mode not in SMOOTH_MODES:
+        raise ValueError(f"mode must be one of {tuple(SMOOTH_MODES)}, got {mode!r}")
+    if len(sigma3) != 3:
+        raise ValueError(f"sigma3 must hold the three sigmas (d, h, w), got {sigma3!r}")
+    if mask is not None and (tuple(mask.shape) != tuple(a.shape[1:]) or mask.dtype.is_floating_point):
+        raise ValueError(f"mask must be bool or integers {tuple(a.shape[1:])}, got {tuple(mask.shape)} {mask.dtype}")
+
+
+def smooth_source_index(n, r, mode, device=None):
+    """(n, 2r+1) int64: the source index of output o and tap i = -r..r on an axis of extent n under `mode`, -1 where the tap
+    contributes 0 ("constant" outside 0..n-1) - the index formulas of include/tmf_hip.h."""
+    j = torch.arange(n, device=device).view(n, 1) + torch.arange(-r, r + 1, device=device).view(1, 2 * r + 1)
+    if mode == "reflect":
+        p = j % (2 * n)                                                     # non-negative for a positive modulus
+        return torch.where(p < n, p, 2 * n - 1 - p)
+    if mode == "nearest":
+        return j.clamp(0, n - 1)
+    return torch.where((j >= 0) & (j < n), j, torch.full_like(j, -1))
+
+
+def _smooth_axis(x, dim, taps, mode):
+    """One 1-D pass along dim: the taps in ascending order, one index_select, one multiply and one add each."""
+    r = (taps.numel() - 1) // 2
+    src = smooth_source_index(x.shape[dim], r, mode, x.device)
+    shape = [1] * x.dim()
+    shape[dim] = x.shape[dim]
+    acc = torch.zeros_like(x)
+    for i, w in enumerate(taps.tolist()):
+        col = src[:, i]
+        term = x.index_select(dim, col.clamp(min=0))
+        if mode == "constant":
+            term = torch.where((col >= 0).view(shape), term, torch.zeros_like(term))
+        acc = acc + w * term
+    return acc
+
+
+def gaussian_smooth_torch(a, sigma3, truncate=4.0, mode="reflect", mask=None):
+    """gaussian_smooth in stock torch ops on whatever device and floating dtype `a` has: per filtered axis one index_select per
+    tap through the index formulas of include/tmf_hip.h, accumulated in ascending tap order; with a mask G(a*m) / G(m) inside
+    and 0 outside.  The taps are the library's (gaussian_taps): the float32 ones for float32 and narrower tensors, which are
+    filtered in float32 and rounded once, the unrounded float64 ones for float64 tensors."""
+    _smooth_args(a, sigma3, truncate, mode, mask)
+    wide = a.dtype if a.dtype in (_f32, torch.float64) else _f32
+    taps = [gaussian_taps(s, truncate, wide) for s in sigma3]
+    x = a.to(wide)
+    inside = None
+    if mask is not None:
+        inside = (mask.to(a.device) != 0).view(1, *a.shape[1:])
+        x = torch.where(inside, x, torch.zeros_like(x))
+        den = inside.to(wide)
+    for dim in (3, 2, 1):                                                       # W, H, D: the order of the kernels
+        t = taps[dim - 1]
+        if t.numel() == 1:
+            continue
+        x = _smooth_axis(x, dim, t, mode)
+        if inside is not None:
+            den = _smooth_axis(den, dim, t, mode)
+    if inside is not None:
+        x = torch.where(inside, x / torch.where(inside, den, torch.ones_like(den)), torch.zeros_like(x))
+    return x.to(a.dtype)
+
+
+def smooth_ok(a, mask=None):
+    """tmf_gaussian_smooth takes these: a contiguous float32 (B, D, H, W) on a HIP device with B <= 65536 and D*H*W < 2^31, the
+    mask (if any) contiguous int32 on the same device."""
+    pairs = [(a, _f32)] + ([(mask, torch.int32)] if mask is not None else [])
+    return _kernel_takes(*pairs) and a.dim() == 4 and a.shape[0] <= 65536 and a[0].numel() < 1 << 31
+
+
+def gaussian_smooth(a, sigma3, truncate=4.0, mode="reflect", mask=None, out=None):
+    """a (B, D, H, W) float32 on a HIP device, sigma3 = (sigma_d, sigma_h, sigma_w) in voxels, mask None or (D, H, W) int32 ->
+    the Gaussian-filtered maps (tmf_gaussian_smooth: two launches, no host read, the same bits on every call); with a mask
+    G(a*m) / G(m) inside it and 0 outside.  The kernel path only: TmfError for tensors it does not take (see smooth_ok;
+    gaussian_smooth_torch is the same function in stock ops), ValueError for arguments the entry refuses."""
+    _smooth_args(a, sigma3, truncate, mode, mask)
+    if not smooth_ok(a, mask):
+        raise _lib.TmfError("gaussian_smooth takes a contiguous float32 (B, D, H, W) tensor (and an int32 mask) on one HIP device")
+    for s in sigma3:
+        smooth_radius(s, truncate)                          # the library's own refusal, as a ValueError, before anything is allocated
+    _chk(a, "a")
+    B, D, H, W = a.shape
+    if out is None:
+        out = torch.empty_like(a)
+    elif out.shape != a.shape or not _kernel_takes((a, _f32), (out, _f32)):
+        raise ValueError(f"out must be a contiguous float32 tensor {tuple(a.shape)} on a's device")
+    nws = _lib.query("tmf_smooth_workspace_bytes", B, D, H, W, int(mask is not None))
+    ws = torch.empty((nws,), device=a.device, dtype=torch.uint8)
+    _lib.call("tmf_gaussian_smooth", a.data_ptr(), _ptr(mask), out.data_ptr(), *(float(s) for s in sigma3), float(truncate),
+              SMOOTH_MODES[mode], ws.data_ptr(), nws, B, D, H, W, _stream())
+    return out
+
+
 class FusionTrain(torch.autograd.Function):
     """CrossTransformer_MOD_AVG forward / backward as ONE library call each (tmf_fusion_train_fwd / _bwd,
     csrc/fusion_path.hip).  forward(mri_tok, pet_tok, cfg, *params): params = per Transformer instance (mri enc of layer

@@ -16,6 +16,7 @@ explanation of the deployed network that leaves its buffers alone."""
 import torch
 
 from ._explain import _check, _Frozen, _int, _logits, _resolve_target
+from .smooth import BLUR_SIGMA, gaussian_smooth
 
 __all__ = ["input_gradients", "integrated_gradients"]
 
@@ -45,13 +46,18 @@ def input_gradients(model, *volumes, target=None, output=0, freeze=True):
 
 def integrated_gradients(model, *volumes, baselines=None, steps=16, target=None, output=0):
     """(volume - baseline) x the mean input gradient along the straight path from baseline to volume: midpoint rule over `steps`
-    points alpha_k = (k + 1/2) / steps, accumulated in fp32 on the device in step order.  baselines None: zeros.  target None is
+    points alpha_k = (k + 1/2) / steps, accumulated in fp32 on the device in step order.  baselines None: zeros; "blur": every
+    volume's own blurred copy, gaussian_smooth(volume, sigma=smooth.BLUR_SIGMA) (the blurred-input baseline).  target None is
     resolved ONCE, at the volume itself (one more forward, without a graph).  In train mode each of these forwards updates the
     BatchNorm buffers and consumes Dropout random numbers (see the module docstring)."""
     _check(volumes)
     _int(steps, "steps must be a positive integer", 1)
     if baselines is None:
         baselines = tuple(torch.zeros_like(v) for v in volumes)
+    elif isinstance(baselines, str):
+        if baselines != "blur":
+            raise ValueError(f"baselines must be None, \"blur\" or one tensor per volume, got {baselines!r}")
+        baselines = tuple(gaussian_smooth(v, sigma=BLUR_SIGMA) for v in volumes)
     elif torch.is_tensor(baselines):
         baselines = (baselines,)
     if len(baselines) != len(volumes) or any(b.shape != v.shape for b, v in zip(baselines, volumes)):
