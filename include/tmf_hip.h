@@ -1202,6 +1202,56 @@ int    tmf_gaussian_smooth(const float* a, const int* mask, float* out, double s
                            double truncate, int mode, void* workspace, size_t workspace_bytes, int B, int D, int H, int W,
                            void* stream);
 
+/* ------------------------------------------------------------------------------
+ * RISE saliency maps (csrc/rise.hip; Petsiuk et al., RISE, 2018): score the network on the volume under N smooth random
+ * masks, add the masks up weighted by their scores.  Black-box like occlusion, but at voxel resolution and with no patch size
+ * to choose.  The reference has no such function; these entries replace the loop its user writes with stock ops: an upsample,
+ * a crop and a multiply per mask - twice, once to perturb and once to accumulate - or N full-resolution masks kept in memory.
+ *
+ * Geometry.  Per axis with extent S and s cells, 1 <= s <= S: cell size c = ceil(S / s), n = s + 2 nodes.  A mask m owns a
+ * node grid g_m[n_d][n_h][n_w] of bytes 0 / 1 and a shift t_m[3] with 0 <= t_a < c_a.  For voxel coordinate v_a:
+ * q = v_a + t_a, i_a = q / c_a (i_a + 1 <= s + 1 always holds), r_a = q % c_a, w1_a = float(r_a) * invc_a with
+ * invc_a = 1.0f / float(c_a) computed once on the host, w0_a = 1.0f - w1_a.
+ * Mask value.  Every operation is rounded on its own, nothing is contracted:
+ *     x[a][b] = g[i_d+a][i_h+b][i_w] * w0_w + g[i_d+a][i_h+b][i_w+1] * w1_w
+ *     y[a]    = x[a][0] * w0_h + x[a][1] * w1_h
+ *     M       = y[0] * w0_d + y[1] * w1_d
+ * so W is interpolated first, then H, then D.  E[M(v)] = p exactly for every voxel, 0 <= M <= 1 + 2^-22, and
+ * |M - M_exact| <= 16 * 2^-24, M_exact the same interpolation with weights r / c in fp64.
+ * Nodes and shifts.  Philox4x32-10 under the key (seed_lo ^ 0x52495345, seed_hi ^ 0x6D61736B).  The node with linear index
+ * e = (i_d * n_h + i_h) * n_w + i_w takes word e & 3 of counter (e >> 2, m, 0, 0) and is 1 iff
+ * float(word >> 8) < float(p) * 2^24.  The shift of axis a is (word_a * c_a) >> 32 in 64-bit arithmetic, from counter
+ * (0, m, 1, 0).  Grids and shifts are a pure function of (seed, m, geometry, p): independent of N, of the chunking and of the call.
+ * Jobs.  Job j = b * N + m is sample b under mask m; the masks are shared by the samples.  The perturbed volume is
+ * out = f + M * (vol - f), each operation rounded on its own, f = base[b][v] where a `base` volume is given (a blurred copy,
+ * for example), else fill[b].  With f = 0 this is M * vol bit for bit, the RISE of the paper.
+ * Map.  sal[b][v] = scale * sum_m scores[b][m] * M_m(v) over m = m_first, m_first + m_step, ... < N: an fp32 chain in
+ * ascending m from 0.0f (one rounded product and one rounded sum per term), then ONE multiplication by scale.  No atomics: two
+ * calls give the same bits, a sample alone gives the bits it has inside a batch.  With n terms,
+ *     |sal - exact| <= scale * (n + 18) * 2^-24 * sum_m |scores[b][m]|     per voxel,
+ * exact with M_exact and fp64 sums.
+ *
+ * tmf_rise_geometry: HOST arrays cell3[3], nodes3[3]; returns the bytes of one node grid, n_d*n_h*n_w, or a negative TMF_E_*.
+ * tmf_rise_masks: nodes [N][n_d][n_h][n_w] bytes and shifts [N][3] int32 of masks m0 .. m0+N-1.  ONE launch.
+ * tmf_rise_apply: out [K][D][H][W] for jobs j0 .. j0+K-1 (nodes / shifts hold masks 0 .. N-1); a chunk may straddle samples.
+ *   ONE launch; 16 bytes per lane where D*H*W % 4 == 0 and vol, out (and base) are 16-byte aligned, one element per lane
+ *   otherwise, with equal bits on both paths.
+ * tmf_rise_accumulate: scores [B][N] -> sal [B][D][H][W], EVERY element written.  ONE launch: a workgroup owns a tile of
+ *   voxels, rebuilds every mask in registers from node grids staged in LDS and feeds up to 8 samples' accumulators per
+ *   evaluation (a larger B in groups of 8); a grid-stride loop over the tiles bounds the grid.
+ * Refusals (negative code, nothing launched, the buffers untouched).  TMF_E_NULL: a null pointer, except fill where base is
+ * given and base where fill is given.  TMF_E_SHAPE: an extent below 1, D*H*W >= 2^31 or a node grid of 2^31 bytes or more; B
+ * outside 1..65536; B*N >= 2^31.  TMF_E_ARG: s outside 1..S; p outside (0, 1) or not finite; N < 1, m0 < 0, m0 + N >= 2^31;
+ * K outside 1..65536, j0 < 0 or j0 + K > B*N; m_step < 1 or m_first outside 0..N-1; out overlapping vol.  TMF_E_ALIGN: a
+ * float or int32 pointer that is not 4-byte aligned. */
+int    tmf_rise_geometry(int D, int H, int W, int sd, int sh, int sw, int* cell3, int* nodes3);
+int    tmf_rise_masks(unsigned char* nodes, int* shifts, int D, int H, int W, int sd, int sh, int sw, float p,
+                      unsigned long long seed, int m0, int N, void* stream);
+int    tmf_rise_apply(const float* vol, const unsigned char* nodes, const int* shifts, const float* fill, const float* base,
+                      float* out, int B, int D, int H, int W, int sd, int sh, int sw, int N, int j0, int K, void* stream);
+int    tmf_rise_accumulate(const float* scores, const unsigned char* nodes, const int* shifts, float* sal, float scale, int B,
+                           int D, int H, int W, int sd, int sh, int sw, int N, int m_first, int m_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

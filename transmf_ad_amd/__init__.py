@@ -25,6 +25,7 @@ from .faithfulness import faithfulness_curve, faithfulness_curve_torch   # noqa:
 from .region_stats import RegionAccumulator, RegionStats, region_stats, region_stats_torch   # noqa: F401
 from .clusters import Clusters, clusters, clusters_torch       # noqa: F401
 from .smooth import gaussian_smooth, gaussian_smooth_torch     # noqa: F401
+from .rise import Rise, rise, rise_torch                       # noqa: F401
 from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, FeedForward, PreNorm,   # noqa: F401
                        Transformer, sNet)
 
@@ -37,4 +38,5 @@ __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_trans
            "grad_cam", "grad_cam_torch", "occlusion_sensitivity", "occlusion_sensitivity_torch",
            "faithfulness_curve", "faithfulness_curve_torch",
            "region_stats", "region_stats_torch", "RegionStats", "RegionAccumulator",
-           "clusters", "clusters_torch", "Clusters", "gaussian_smooth", "gaussian_smooth_torch"]
+           "clusters", "clusters_torch", "Clusters", "gaussian_smooth", "gaussian_smooth_torch",
+           "rise", "rise_torch", "Rise"]

@@ -14,7 +14,7 @@
 //
 // Numerics: fp32 fma chains in k order per output; BatchNorm1d as torch (biased variance for normalisation, unbiased
 // into running_var, momentum, eps); Dropout by a caller-supplied keep-mask already scaled by 1 / (1 - p) (NULL = none).
-#include "tmf_common.h"
+#include "tmf_device.h"
 
 namespace {
 
@@ -928,20 +928,6 @@ int check_params(const char* fn, const tmf_heads_params* p) {
 }  // namespace
 
 namespace {
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words.  Counter-based, so a keep-mask
-// is a pure function of (seed, call offset, element index): no generator state on the device, reproducible under a seed.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // Scaled Dropout keep-masks of up to TMF_MASK_SEGMENTS tensors in ONE launch: element e of segment s is 1 / keep_s with
 // probability keep_s, else 0 (u = 24 random bits; keep iff u < keep * 2^24).  Four elements per Philox call.
 struct MaskSeg { float* out; long n; float keep, inv; };

@@ -100,6 +100,21 @@ __device__ __forceinline__ void split3_rne(float a, unsigned short& h, unsigned 
     l = bf16_bits_rne(r2);
 }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words ----------------------------------
+// Counter-based, so a draw is a pure function of (seed, counter): no generator state on the device, reproducible under a seed.
+// The Dropout keep-masks of heads.hip and the RISE node grids and shifts of rise.hip; each keys it with its own domain constant.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- the order-preserving uint32 image of a float ------------------------------------------------------------------------------
 // ascending key <=> ascending a = x + 0.0f as floats (-0.0 ranks with +0.0; infinities are ordinary values).  The radix select of
 // faithfulness.hip and the packed max / argmax of region_stats.hip.

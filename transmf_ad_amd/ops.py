@@ -1521,6 +1521,224 @@ def occlusion_volume(drops, size, patch=None, stride=None, labels=None):
 
 
 # --------------------------------------------------------------------------------------
+# RISE saliency maps (csrc/rise.hip; include/tmf_hip.h states the geometry, the mask value, the nodes and shifts, the jobs and the map)
+# --------------------------------------------------------------------------------------
+
+RISE_KEY = (0x52495345, 0x6D61736B)      # XORed into the two halves of the seed
+
+
+def _cells3(cells):
+    c = (cells,) * 3 if _is_int(cells) else tuple(cells) if isinstance(cells, (tuple, list)) else None
+    if c is None or len(c) != 3 or any(not _is_int(x) for x in c):
+        raise ValueError(f"cells must be an int or three of them, got {cells!r}")
+    return c
+
+
+def rise_geometry(size, cells):
+    """-> (cell (c_d, c_h, c_w), nodes (n_d, n_h, n_w), the bytes of one node grid): per axis c = ceil(S / s), n = s + 2
+    (tmf_rise_geometry computes the same); ValueError unless 1 <= s <= S on every axis."""
+    size, cells = tuple(int(s) for s in size), _cells3(cells)
+    if len(size) != 3 or any(S < 1 for S in size):
+        raise ValueError(f"size must be three positive extents, got {size}")
+    if any(not 1 <= s <= S for S, s in zip(size, cells)):
+        raise ValueError(f"cells {cells} must lie in 1..extent {size} on every axis")
+    nodes = tuple(s + 2 for s in cells)
+    return tuple(-(-S // s) for S, s in zip(size, cells)), nodes, nodes[0] * nodes[1] * nodes[2]
+
+
+def rise_ok(*tensors):
+    """The RISE kernels take these: contiguous float32 (uint8 nodes, int32 shifts) tensors on one HIP device, none empty."""
+    return _kernel_takes(*((t, (_f32, torch.uint8, torch.int32)) for t in tensors))
+
+
+def _rise_mask_args(size, cells, p, seed, m0, N):
+    geom = rise_geometry(size, cells)
+    if not isinstance(p, (int, float)) or isinstance(p, bool) or not 0.0 < float(p) < 1.0:
+        raise ValueError(f"p must lie in (0, 1), got {p!r}")
+    if not _is_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
+    if not (_is_int(m0) and _is_int(N) and N >= 1 and m0 >= 0 and m0 + N < 1 << 31):
+        raise ValueError(f"masks m0 = {m0!r}, N = {N!r}")
+    return geom
+
+
+def _rise_masks_host(cell, nodes, G, p, seed, m0, N):
+    """The node bytes and shifts as the header defines them, in numpy on the host: what rise_masks_torch falls back to where
+    no HIP device can run tmf_rise_masks."""
+    import numpy as np
+    u64, mask32 = np.uint64, np.uint64(0xFFFFFFFF)
+
+    def philox(c0, c1, c2, c3):
+        c0, c1, c2, c3 = (np.asarray(c, dtype=u64) for c in np.broadcast_arrays(c0, c1, c2, c3))
+        k0, k1 = u64((seed & 0xFFFFFFFF) ^ RISE_KEY[0]), u64((seed >> 32) ^ RISE_KEY[1])
+        for _ in range(10):
+            p0, p1 = u64(0xD2511F53) * c0, u64(0xCD9E8D57) * c2
+            c0, c1, c2, c3 = (p1 >> u64(32)) ^ c1 ^ k0, p1 & mask32, (p0 >> u64(32)) ^ c3 ^ k1, p0 & mask32
+            k0, k1 = (k0 + u64(0x9E3779B9)) & mask32, (k1 + u64(0xBB67AE85)) & mask32
+        return np.stack([c0, c1, c2, c3], -1)
+
+    m = np.arange(m0, m0 + N, dtype=u64)
+    nq = (G + 3) // 4
+    words = philox(np.arange(nq, dtype=u64)[None, :], m[:, None], 0, 0).reshape(N, nq * 4)[:, :G]
+    thr = np.float32(p) * np.float32(16777216.0)
+    grid = ((words >> u64(8)).astype(np.float32) < thr).astype(np.uint8).reshape((N,) + tuple(nodes))
+    sw = philox(0, m, 1, 0)[:, :3]
+    shifts = ((sw * np.asarray(cell, dtype=u64)) >> u64(32)).astype(np.int32)
+    return torch.from_numpy(grid), torch.from_numpy(shifts)
+
+
+def rise_masks(size, cells, p, seed, m0, N, device):
+    """nodes (N, n_d, n_h, n_w) uint8 and shifts (N, 3) int32 of masks m0 .. m0+N-1 on `device`: a pure function of (seed, m,
+    geometry, p).  A HIP device: ONE launch (tmf_rise_masks); anything else: rise_masks_torch."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return rise_masks_torch(size, cells, p, seed, m0, N, device)
+    _cell, nn, _G = _rise_mask_args(size, cells, p, seed, m0, N)
+    with torch.cuda.device(device):
+        nodes = torch.empty((N,) + nn, device=device, dtype=torch.uint8)
+        shifts = torch.empty((N, 3), device=device, dtype=torch.int32)
+        _lib.call("tmf_rise_masks", nodes.data_ptr(), shifts.data_ptr(), *tuple(size), *_cells3(cells), float(p), seed, m0, N,
+                  _stream())
+    return nodes, shifts
+
+
+def rise_masks_torch(size, cells, p, seed, m0, N, device=None):
+    """rise_masks for any device: the nodes and shifts come from the library where a HIP device can run it (then copied to
+    `device`), else from the same Philox4x32-10 restated in numpy on the host - the same bytes either way."""
+    device = torch.device("cpu" if device is None else device)
+    if torch.cuda.is_available():
+        nodes, shifts = rise_masks(size, cells, p, seed, m0, N, device if device.type == "cuda" else torch.device("cuda"))
+        return nodes.to(device), shifts.to(device)
+    cell, nn, G = _rise_mask_args(size, cells, p, seed, m0, N)
+    nodes, shifts = _rise_masks_host(cell, nn, G, p, seed, m0, N)
+    return nodes.to(device), shifts.to(device)
+
+
+def _rise_args(nodes, shifts, size, cells):
+    cell, nn, _G = rise_geometry(size, cells)
+    N = nodes.shape[0]
+    if nodes.dtype != torch.uint8 or tuple(nodes.shape) != (N,) + nn or N < 1:
+        raise ValueError(f"nodes must be uint8 (N, {nn[0]}, {nn[1]}, {nn[2]}), got {tuple(nodes.shape)} {nodes.dtype}")
+    if shifts.dtype != torch.int32 or tuple(shifts.shape) != (N, 3):
+        raise ValueError(f"shifts must be int32 ({N}, 3), got {tuple(shifts.shape)} {shifts.dtype}")
+    return cell, N
+
+
+def rise_mask_values(nodes, shifts, size, cells, dtype=_f32):
+    """M of every mask in nodes / shifts on the voxel grid -> (n, D, H, W): THE formula of the header, op by op - W first, then
+    H, then D, every product and sum a torch op of its own.  float32: w1 = float(r) * (1.0f / float(c)), the kernels' bits;
+    float64: w1 = r / c, M_exact.  Any other floating dtype: the float32 values cast."""
+    import numpy as np
+    cell, _N = _rise_args(nodes, shifts, size, cells)
+    exact = dtype == torch.float64
+    ct = torch.float64 if exact else _f32
+    dev = nodes.device
+    idx, w0, w1 = [], [], []
+    for a in range(3):
+        q = torch.arange(size[a], device=dev).view(1, -1) + shifts[:, a:a + 1].to(device=dev, dtype=torch.long)     # (n, S)
+        i = q // cell[a]
+        r = (q - i * cell[a]).to(ct)
+        w = r / cell[a] if exact else r * float(np.float32(1.0) / np.float32(cell[a]))
+        shape = [-1, 1, 1, 1]
+        shape[a + 1] = size[a]
+        idx.append(i.view(shape))
+        w1.append(w.view(shape))
+        w0.append((1.0 - w).view(shape))
+    m = torch.arange(nodes.shape[0], device=dev).view(-1, 1, 1, 1)
+    g = lambda a, b, c: nodes[m, idx[0] + a, idx[1] + b, idx[2] + c].to(ct)
+    x = [[g(a, b, 0) * w0[2] + g(a, b, 1) * w1[2] for b in (0, 1)] for a in (0, 1)]
+    y = [x[a][0] * w0[1] + x[a][1] * w1[1] for a in (0, 1)]
+    M = y[0] * w0[0] + y[1] * w1[0]
+    return M if M.dtype == dtype else M.to(dtype)
+
+
+def _rise_apply_args(vol, nodes, shifts, fill, size, cells, j0, K, base, out):
+    _cell, N = _rise_args(nodes, shifts, size, cells)
+    B = vol.shape[0]
+    if tuple(vol.shape[-3:]) != tuple(size) or vol.numel() != B * size[0] * size[1] * size[2]:
+        raise ValueError(f"vol must be a one-channel volume (B, 1, D, H, W) or (B, D, H, W) of {tuple(size)} voxels, got {tuple(vol.shape)}")
+    if base is not None and tuple(base.shape) != tuple(vol.shape):
+        raise ValueError(f"base must have vol's shape {tuple(vol.shape)}, got {tuple(base.shape)}")
+    if base is None and (fill is None or tuple(fill.shape) != (B,)):
+        raise ValueError(f"fill must be ({B},), got {None if fill is None else tuple(fill.shape)}")
+    _job_range(B, N, j0, K)
+    return _job_buffer(vol, K, out), N
+
+
+def _rise_apply_rows(vol, nodes, shifts, fill, size, cells, N, j0, K, base, out):
+    jobs = torch.arange(j0, j0 + K, device=vol.device)
+    b, m = jobs // N, (jobs % N).to(nodes.device)
+    dtype = torch.float64 if vol.dtype == torch.float64 else _f32
+    M = rise_mask_values(nodes.index_select(0, m), shifts.index_select(0, m), size, cells, dtype).to(vol.device)
+    M = M.view((K,) + (1,) * (vol.dim() - 4) + tuple(size))
+    v = vol.index_select(0, b).to(dtype)
+    f = base.index_select(0, b).to(dtype) if base is not None else fill.index_select(0, b).to(dtype).view((K,) + (1,) * (vol.dim() - 1))
+    out.copy_(f + M * (v - f))
+    return out
+
+
+def rise_apply_torch(vol, nodes, shifts, fill, size, cells, j0, K, base=None, out=None):
+    """rise_apply in plain torch ops on whatever device and floating dtype vol has: f + M * (vol - f) with rise_mask_values
+    (float32, or float64 for a float64 vol), three torch ops."""
+    out, N = _rise_apply_args(vol, nodes, shifts, fill, size, cells, j0, K, base, out)
+    return _rise_apply_rows(vol, nodes, shifts, fill, size, cells, N, j0, K, base, out)
+
+
+def rise_apply(vol, nodes, shifts, fill, size, cells, j0, K, base=None, out=None):
+    """out[k] = f + M_m * (vol[b] - f) for job j0 + k = b*N + m: vol (B, 1, D, H, W) or (B, D, H, W), nodes / shifts of masks
+    0..N-1, f = base[b] (a tensor of vol's shape) where given, else fill[b] (fill (B,)) -> (K, ...) of vol's shape.  Contiguous
+    float32 HIP tensors: ONE launch (tmf_rise_apply); anything else: rise_apply_torch, the same bits in float32."""
+    out, N = _rise_apply_args(vol, nodes, shifts, fill, size, cells, j0, K, base, out)
+    if not (rise_ok(vol, nodes, shifts, base if base is not None else fill, out) and vol.dtype == _f32 and out.dtype == _f32
+            and (base if base is not None else fill).dtype == _f32):
+        return _rise_apply_rows(vol, nodes, shifts, fill, size, cells, N, j0, K, base, out)
+    _chk(vol, "vol")
+    _lib.call("tmf_rise_apply", vol.data_ptr(), nodes.data_ptr(), shifts.data_ptr(), _ptr(None if base is not None else fill),
+              _ptr(base), out.data_ptr(), vol.shape[0], *tuple(size), *_cells3(cells), N, j0, K, _stream())
+    return out
+
+
+def _rise_accumulate_args(scores, nodes, shifts, size, cells, m_first, m_step):
+    _cell, N = _rise_args(nodes, shifts, size, cells)
+    if scores.dim() != 2 or scores.shape[1] != N or scores.shape[0] < 1 or not scores.dtype.is_floating_point:
+        raise ValueError(f"scores must be floating-point (B, {N}), got {tuple(scores.shape)} {scores.dtype}")
+    if not (_is_int(m_first) and _is_int(m_step) and m_step >= 1 and 0 <= m_first < N):
+        raise ValueError(f"masks m_first = {m_first!r}, m_step = {m_step!r} of {N}")
+    return N
+
+
+def rise_accumulate_torch(scores, nodes, shifts, size, cells, scale=1.0, m_first=0, m_step=1, chunk=64):
+    """rise_accumulate in plain torch ops on whatever device and floating dtype the scores have: a matmul of the scores with
+    rise_mask_values, `chunk` rebuilt masks at a time, then one multiplication by scale.  float64 scores: M_exact and fp64 sums,
+    the reference of the bound."""
+    N = _rise_accumulate_args(scores, nodes, shifts, size, cells, m_first, m_step)
+    B, size = scores.shape[0], tuple(size)
+    dtype = torch.float64 if scores.dtype == torch.float64 else _f32
+    ms = torch.arange(m_first, N, m_step, device=nodes.device)
+    acc = torch.zeros((B, size[0] * size[1] * size[2]), device=scores.device, dtype=dtype)
+    for lo in range(0, ms.numel(), chunk):
+        m = ms[lo:lo + chunk]
+        M = rise_mask_values(nodes.index_select(0, m), shifts.index_select(0, m), size, cells, dtype).to(scores.device)
+        acc += scores.index_select(1, m.to(scores.device)).to(dtype) @ M.view(m.numel(), -1)
+    return (acc * scale).to(scores.dtype).view((B,) + size)
+
+
+def rise_accumulate(scores, nodes, shifts, size, cells, scale=1.0, m_first=0, m_step=1):
+    """sal[b] = scale * sum_m scores[b, m] * M_m over m = m_first, m_first + m_step, ... < N: scores (B, N) -> (B, D, H, W), an
+    fp32 chain in ascending m and one multiplication by scale.  Contiguous float32 HIP scores: ONE launch (tmf_rise_accumulate),
+    every mask rebuilt in registers, no atomics, two calls give the same bits; anything else: rise_accumulate_torch."""
+    N = _rise_accumulate_args(scores, nodes, shifts, size, cells, m_first, m_step)
+    if not (rise_ok(scores, nodes, shifts) and scores.dtype == _f32):
+        return rise_accumulate_torch(scores, nodes, shifts, size, cells, scale, m_first, m_step)
+    _chk(scores, "scores")
+    B, size = scores.shape[0], tuple(size)
+    sal = torch.empty((B,) + size, device=scores.device, dtype=_f32)
+    _lib.call("tmf_rise_accumulate", scores.data_ptr(), nodes.data_ptr(), shifts.data_ptr(), sal.data_ptr(), float(scale), B, *size,
+              *_cells3(cells), N, m_first, m_step, _stream())
+    return sal
+
+
+# --------------------------------------------------------------------------------------
 # deletion / insertion curves (csrc/faithfulness.hip; include/tmf_hip.h states the ordering, the thresholds and the jobs)
 # --------------------------------------------------------------------------------------
 
