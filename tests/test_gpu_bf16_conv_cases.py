@@ -14,21 +14,12 @@ import pytest
 import torch
 
 import _bf16_conv_cases as K
+from _conv_util import _lib, _ops
 from test_gpu_bn_reduce import Arena
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN_BYTE = 0xFF
-
-
-def _lib():
-    from transmf_ad_amd import _lib
-    return _lib
-
-
-def _ops():
-    from transmf_ad_amd import ops
-    return ops
 
 
 def _st():

@@ -12,40 +12,13 @@ import torch
 import torch.nn.functional as F
 
 import _conv_variants as V
+from _conv_util import _lib, _ncdhw, _ndhwc, _ops, _rand, _relerr
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 SLOPE = float(np.float32(0.01))
 POOLS = (None, "max", "avg")
-
-
-def _ops():
-    from transmf_ad_amd import ops
-    return ops
-
-
-def _lib():
-    from transmf_ad_amd import _lib
-    return _lib
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    rs = np.random.RandomState(seed)
-    return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32))
-
-
-def _ndhwc(x):
-    return x.permute(0, 2, 3, 4, 1).contiguous()
-
-
-def _ncdhw(x):
-    return x.permute(0, 4, 1, 2, 3).contiguous()
-
-
-def _relerr(got, ref):
-    ref = ref.double()
-    return ((got.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
 
 
 def _say(row, what, value):

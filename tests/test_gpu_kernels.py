@@ -7,27 +7,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _conv_util import _ncdhw, _ndhwc, _ops, _rand, _relerr
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _ops():
-    from transmf_ad_amd import ops
-    return ops
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    rs = np.random.RandomState(seed)
-    return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32))
-
-
-def _ndhwc(x):      # (B,C,D,H,W) -> (B,D,H,W,C) contiguous
-    return x.permute(0, 2, 3, 4, 1).contiguous()
-
-
-def _ncdhw(x):
-    return x.permute(0, 4, 1, 2, 3).contiguous()
 
 
 @pytest.fixture(params=[(0, 1), (2, 1), (2, 0)], ids=["small-brick", "8x8x8-brick", "8x8x8-brick-register-staged"])
@@ -41,11 +25,6 @@ def bf16_kernel_choice(request):
     yield request.param[0]
     _lib.call("tmf_set_option", b"bf16_v2", 1)
     _lib.call("tmf_set_option", b"bf16_dma", 1)
-
-
-def _relerr(got, ref):
-    ref = ref.double()
-    return ((got.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
 
 
 CONV_SHAPES = [

@@ -6,32 +6,15 @@ epilogue (role coefficients, statistic cells kept in registers over an item) in 
 tolerances of test_conv3d_winograd_weight_gradient / test_conv3d_winograd_split_kernel (test_gpu_kernels.py); the statistic rows
 against the sums of the z the kernel itself wrote at 2e-7; every output repeats bit for bit.  Measured on an MI355X: dw 2.2 - 3.0e-7,
 z and dx 2.4 - 3.5e-7, the rows 2.0e-9 - 2.7e-8 (sums) and 1.7 - 6.3e-8 (sums of squares)."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from _conv_util import _ncdhw, _ndhwc, _rand, _relerr
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    rs = np.random.RandomState(seed)
-    return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32))
-
-
-def _ndhwc(x):
-    return x.permute(0, 2, 3, 4, 1).contiguous()
-
-
-def _ncdhw(x):
-    return x.permute(0, 4, 1, 2, 3).contiguous()
-
-
-def _relerr(got, ref):
-    ref = ref.double()
-    return ((got.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
 
 
 def _stages(shape, geom):

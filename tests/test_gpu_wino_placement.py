@@ -1,32 +1,15 @@
 """The persistent Winograd kernels at grids that are NO multiple of 8 (where their XCD placement used to be switched off) against
 fp64 torch: forward with statistic partials, data gradient, weight gradient, run-to-run bits.  Tolerances: those of
 test_conv3d_winograd_split_kernel / test_conv3d_winograd_weight_gradient (test_gpu_kernels.py)."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from _conv_util import _ncdhw, _ndhwc, _rand, _relerr
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    rs = np.random.RandomState(seed)
-    return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32))
-
-
-def _ndhwc(x):
-    return x.permute(0, 2, 3, 4, 1).contiguous()
-
-
-def _ncdhw(x):
-    return x.permute(0, 4, 1, 2, 3).contiguous()
-
-
-def _relerr(got, ref):
-    ref = ref.double()
-    return ((got.double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
 
 
 # (B, D, H, W, cin, cout), items of the split kernel's forward launch, its grid on 256 compute units

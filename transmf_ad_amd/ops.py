@@ -6,6 +6,7 @@ fp32, contiguous, on a HIP device; activations are channels-last (B, D, H, W, C)
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -200,18 +201,6 @@ def pack_weights_wino(weight: torch.Tensor, want_fwd: bool = True, want_dgrad: b
     return uf, ud
 
 
-def conv3d_wino_raw(x, u, cin, cout, want_stats):
-    """3x3x3 convolution in the Winograd form F(2x2x2, 3x3x3) (csrc/conv3d_wino.hip); u from pack_weights_wino."""
-    B, D, H, W = x.shape[:4]
-    z = torch.empty((B, D, H, W, cout), device=x.device, dtype=_f32)
-    part, nblk = None, 0
-    if want_stats:
-        nblk = _lib.query("tmf_conv3d_wino_stat_blocks", B, D, H, W)
-        part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
-    _lib.call("tmf_conv3d_fwd_wino", x.data_ptr(), u.data_ptr(), z.data_ptr(), _ptr(part), B, D, H, W, cin, cout, _stream())
-    return z, part, nblk
-
-
 def wino_p_mode() -> bool:
     """True when the Winograd entries run their persistent one-wave-per-SIMD kernels (the default; TMF_WINO_P=0 or
     tmf_set_option("wino_p", 0): the two-waves-per-SIMD kernels of round 4)."""
@@ -222,95 +211,162 @@ def wgrad_wino_ok(cin: int, cout: int) -> bool:
     return bool(_lib.query("tmf_conv3d_wgrad_wino_ok", cin, cout))
 
 
-def conv3d_wgrad_wino(x, dz, cin, cout, reference_layout=False):
-    """3x3x3 weight gradient in the Winograd form (csrc/conv3d_wino.hip): tap-major [27][cin][cout] or nn.Conv3d's layout."""
+# One row per kernel family of conv_block_algo.  pack(weight, want_fwd, want_dgrad) -> (forward form, data-gradient form) is the
+# family's one-launch packer (the data gradient is the forward entry on the other form with the channel roles swapped; the
+# bf16 and split packers always write the forward form); w16: the packed forms are bf16; io16: the entries read and write
+# fp32 or bf16 activations and take an io word that says which (every other family: fp32 only).  An entry stands with the
+# scalars it takes behind B, D, H, W; a weight gradient's workspace query takes the same ones.  affine: the forward with the
+# eval-mode BatchNorm, LeakyReLU and pool in its epilogue (conv_bn_act_pool_eval_fused).
+_ConvFamily = collections.namedtuple("_ConvFamily", "pack w16 io16 fwd blocks affine wgrad wbytes", defaults=(None, None, None))
+_cck = lambda cin, cout, k: (cin, cout, k)
+_cc = lambda cin, cout, k: (cin, cout)
+_co = lambda cin, cout, k: (cout,)
+_none = lambda cin, cout, k: ()
+_pack_direct = lambda w, f, d: pack_weights_both(w, d, want_fwd=f)
+_DIRECT = _ConvFamily(_pack_direct, False, False, ("tmf_conv3d_fwd", _cck), ("tmf_conv3d_stat_blocks", _cck),
+                      "tmf_conv3d_fwd_affine", ("tmf_conv3d_wgrad", _cck), "tmf_conv3d_wgrad_workspace_bytes")
+_DIRECT_C1 = _ConvFamily(_pack_direct, False, False, ("tmf_conv3d_c1_fwd", _co), ("tmf_conv3d_c1_stat_blocks", _co),
+                         None, ("tmf_conv3d_c1_wgrad", _co), "tmf_conv3d_c1_wgrad_workspace_bytes")     # cin == 1, k == 3
+_WINO = _ConvFamily(pack_weights_wino, False, False, ("tmf_conv3d_fwd_wino", _cc), ("tmf_conv3d_wino_stat_blocks", _none),
+                    "tmf_conv3d_fwd_wino_affine", ("tmf_conv3d_wgrad_wino", _cc), "tmf_conv3d_wgrad_wino_workspace_bytes")
+_BF16 = _ConvFamily(lambda w, f, d: pack_weights_both_bf16(w, d), True, True, ("tmf_conv3d_fwd_bf16_t", _cc),
+                    ("tmf_conv3d_bf16_stat_blocks", _none), None, ("tmf_conv3d_wgrad_bf16_t", _cc),
+                    "tmf_conv3d_wgrad_bf16_workspace_bytes")
+_SPLIT = _ConvFamily(lambda w, f, d: pack_weights_split3(w, d), True, False, ("tmf_conv3d_fwd_split", _cc),
+                     ("tmf_conv3d_split_stat_blocks", _none))                                # (no weight gradient of its own)
+_CONV = {_lib.CONV_DIRECT: _DIRECT, _lib.CONV_WINO: _WINO, _lib.CONV_BF16: _BF16, _lib.CONV_SPLIT: _SPLIT}
+
+
+def _conv_variant(fam, cin, k):
+    return _DIRECT_C1 if (fam is _DIRECT and cin == 1 and k == 3) else fam
+
+
+def _conv_forward(fam, x, w, cin, cout, k, want_stats, out_bf16=False):
+    """z = conv(x, w) on NDHWC x by the entries of one _ConvFamily, w its packed forward form (or, for a data gradient, its
+    dgrad form with cin and cout swapped); returns (z, stat_partial or None, nblk)."""
+    fam = _conv_variant(fam, cin, k)
+    if out_bf16 and not fam.io16:
+        raise _lib.TmfError("only the bf16 convolution kernels write a bf16 tensor")
     B, D, H, W = x.shape[:4]
-    dw = torch.empty((cout, cin, 3, 3, 3) if reference_layout else (27, cin, cout), device=x.device, dtype=_f32)
-    nbytes = _lib.query("tmf_conv3d_wgrad_wino_workspace_bytes", B, D, H, W, cin, cout)
+    z = torch.empty((B, D, H, W, cout), device=x.device, dtype=_b16 if out_bf16 else _f32)
+    part, nblk = None, 0
+    if want_stats:
+        nblk = _lib.query(fam.blocks[0], B, D, H, W, *fam.blocks[1](cin, cout, k))
+        part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
+    io = ((1 if x.dtype == _b16 else 0) | (2 if out_bf16 else 0),) if fam.io16 else ()
+    _lib.call(fam.fwd[0], x.data_ptr(), w.data_ptr(), z.data_ptr(), _ptr(part),
+              B, D, H, W, *fam.fwd[1](cin, cout, k), *io, _stream())
+    return z, part, nblk
+
+
+def _conv_wgrad(fam, x, dz, cin, cout, k, reference_layout):
+    """weight gradient by the entries of one _ConvFamily: tap-major [k^3][cin][cout], or (reference_layout) nn.Conv3d's
+    (cout, cin, k, k, k) written directly by the final reduction."""
+    fam = _conv_variant(fam, cin, k)
+    if fam.wgrad is None:
+        raise _lib.TmfError("this convolution family has no weight-gradient kernel")
+    B, D, H, W = x.shape[:4]
+    dw = torch.empty((cout, cin, k, k, k) if reference_layout else (k ** 3, cin, cout), device=x.device, dtype=_f32)
+    tail = fam.wgrad[1](cin, cout, k)
+    nbytes = _lib.query(fam.wbytes, B, D, H, W, *tail)
     ws = torch.empty((max(nbytes, 16) // 4,), device=x.device, dtype=_f32)
-    _lib.call("tmf_conv3d_wgrad_wino", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes,
-              B, D, H, W, cin, cout, int(reference_layout), _stream())
+    io = ()
+    if fam.io16:
+        if x.dtype != dz.dtype:                  # mixed storage (not produced by sNet): widen the bf16 side
+            x, dz = x.float(), dz.float()
+        io = (1 if x.dtype == _b16 else 0,)
+    _lib.call(fam.wgrad[0], x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes,
+              B, D, H, W, *tail, *io, int(reference_layout), _stream())
     return dw
 
 
-def conv3d_split_raw(x, w3, cin, cout, want_stats):
-    """fp32-accurate conv on the bf16 matrix cores; w3 = split3_bf16(packed [27][cout][cin] fp32 weights)."""
-    B, D, H, W = x.shape[:4]
-    z = torch.empty((B, D, H, W, cout), device=x.device, dtype=_f32)
-    part, nblk = None, 0
-    if want_stats:
-        nblk = _lib.query("tmf_conv3d_split_stat_blocks", B, D, H, W)
-        part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
-    _lib.call("tmf_conv3d_fwd_split", x.data_ptr(), w3.data_ptr(), z.data_ptr(), _ptr(part),
-              B, D, H, W, cin, cout, _stream())
-    return z, part, nblk
+def _pack_conv_weights(weight, fam_f, fam_d, want_dgrad):
+    """(forward form for fam_f, data-gradient form for fam_d or None), one launch per packer that has a form to write."""
+    if fam_d is fam_f or not want_dgrad or fam_f.w16:
+        # (a bf16 or split forward whose data gradient is direct, cout % 8 != 0, packs no form for it: backward's pack_weight_dgrad)
+        return fam_f.pack(weight, True, want_dgrad and fam_d is fam_f)
+    wf = wd = None                                # one direction direct, the other Winograd: the direct packer first
+    for fam in (_DIRECT, _WINO):
+        f, d = fam.pack(weight, fam is fam_f, fam is fam_d)
+        wf, wd = f if fam is fam_f else wf, d if fam is fam_d else wd
+    return wf, wd
+
+
+def conv3d_raw(x, w_packed, cin, cout, ksize, want_stats):
+    """z = conv(x, w) on NDHWC x; returns (z, stat_partial or None, nblk)."""
+    return _conv_forward(_DIRECT, x, w_packed, cin, cout, ksize, want_stats)
 
 
 def conv3d_bf16_raw(x, w_bf16, cin, cout, want_stats, out_bf16=False):
     """z = conv3x3x3(bf16(x), w_bf16) with fp32 accumulation; x may be an fp32 or a bf16 tensor, z is fp32 or
     (out_bf16) bf16; returns (z, stat_partial or None, nblk)."""
-    B, D, H, W = x.shape[:4]
-    z = torch.empty((B, D, H, W, cout), device=x.device, dtype=_b16 if out_bf16 else _f32)
-    part, nblk = None, 0
-    if want_stats:
-        nblk = _lib.query("tmf_conv3d_bf16_stat_blocks", B, D, H, W)
-        part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
-    io = (1 if x.dtype == _b16 else 0) | (2 if out_bf16 else 0)
-    _lib.call("tmf_conv3d_fwd_bf16_t", x.data_ptr(), w_bf16.data_ptr(), z.data_ptr(), _ptr(part),
-              B, D, H, W, cin, cout, io, _stream())
-    return z, part, nblk
+    return _conv_forward(_BF16, x, w_bf16, cin, cout, 3, want_stats, out_bf16)
 
 
-def conv3d_raw(x, w_packed, cin, cout, ksize, want_stats):
-    """z = conv(x, w) on NDHWC x; returns (z, stat_partial or None, nblk)."""
-    B, D, H, W = x.shape[:4]
-    z = torch.empty((B, D, H, W, cout), device=x.device, dtype=_f32)
-    part, nblk = None, 0
-    if cin == 1 and ksize == 3:
-        if want_stats:
-            nblk = _lib.query("tmf_conv3d_c1_stat_blocks", B, D, H, W, cout)
-            part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
-        _lib.call("tmf_conv3d_c1_fwd", x.data_ptr(), w_packed.data_ptr(), z.data_ptr(), _ptr(part),
-                  B, D, H, W, cout, _stream())
-    else:
-        if want_stats:
-            nblk = _lib.query("tmf_conv3d_stat_blocks", B, D, H, W, cin, cout, ksize)
-            part = torch.empty((nblk, 2, cout), device=x.device, dtype=_f32)
-        _lib.call("tmf_conv3d_fwd", x.data_ptr(), w_packed.data_ptr(), z.data_ptr(), _ptr(part),
-                  B, D, H, W, cin, cout, ksize, _stream())
-    return z, part, nblk
+def conv3d_split_raw(x, w3, cin, cout, want_stats):
+    """fp32-accurate conv on the bf16 matrix cores; w3 = split3_bf16(packed [27][cout][cin] fp32 weights)."""
+    return _conv_forward(_SPLIT, x, w3, cin, cout, 3, want_stats)
+
+
+def conv3d_wino_raw(x, u, cin, cout, want_stats):
+    """3x3x3 convolution in the Winograd form F(2x2x2, 3x3x3) (csrc/conv3d_wino.hip); u from pack_weights_wino."""
+    return _conv_forward(_WINO, x, u, cin, cout, 3, want_stats)
+
+
+def conv3d_wgrad(x, dz, cin, cout, ksize, reference_layout=False):
+    """weight gradient: tap-major [k^3][cin][cout], or (reference_layout) nn.Conv3d's (cout, cin, k, k, k)."""
+    return _conv_wgrad(_DIRECT, x, dz, cin, cout, ksize, reference_layout)
 
 
 def conv3d_wgrad_bf16(x, dz, cin, cout, reference_layout=False):
     """weight gradient on the bf16 matrix cores (operands rounded to bf16): tap-major [27][cin][cout], or
     (reference_layout) the nn.Conv3d layout (cout, cin, 3, 3, 3) written directly by the final reduction."""
-    B, D, H, W = x.shape[:4]
-    dw = torch.empty((cout, cin, 3, 3, 3) if reference_layout else (27, cin, cout), device=x.device, dtype=_f32)
-    nbytes = _lib.query("tmf_conv3d_wgrad_bf16_workspace_bytes", B, D, H, W, cin, cout)
-    ws = torch.empty((max(nbytes, 16) // 4,), device=x.device, dtype=_f32)
-    if x.dtype != dz.dtype:                      # mixed storage (not produced by sNet): widen the bf16 side
-        x, dz = x.float(), dz.float()
-    _lib.call("tmf_conv3d_wgrad_bf16_t", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes,
-              B, D, H, W, cin, cout, 1 if x.dtype == _b16 else 0, int(reference_layout), _stream())
-    return dw
+    return _conv_wgrad(_BF16, x, dz, cin, cout, 3, reference_layout)
 
 
-def conv3d_wgrad(x, dz, cin, cout, ksize, reference_layout=False):
-    """weight gradient: tap-major [k^3][cin][cout], or (reference_layout) nn.Conv3d's (cout, cin, k, k, k)."""
-    B, D, H, W = x.shape[:4]
-    dw = torch.empty((cout, cin, ksize, ksize, ksize) if reference_layout else (ksize ** 3, cin, cout),
-                     device=x.device, dtype=_f32)
-    if cin == 1 and ksize == 3:
-        nbytes = _lib.query("tmf_conv3d_c1_wgrad_workspace_bytes", B, D, H, W, cout)
-        ws = torch.empty((max(nbytes, 16) // 4,), device=x.device, dtype=_f32)
-        _lib.call("tmf_conv3d_c1_wgrad", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes,
-                  B, D, H, W, cout, int(reference_layout), _stream())
+def conv3d_wgrad_wino(x, dz, cin, cout, reference_layout=False):
+    """3x3x3 weight gradient in the Winograd form (csrc/conv3d_wino.hip): tap-major [27][cin][cout] or nn.Conv3d's layout."""
+    return _conv_wgrad(_WINO, x, dz, cin, cout, 3, reference_layout)
+
+
+def _bn_eval_coeffs(gamma, beta, bias, running_mean, running_var, eps, cout, dev):
+    """(scale, shift) of eval-mode BatchNorm with the conv bias folded into the shift."""
+    scale = torch.empty(cout, device=dev, dtype=_f32)
+    shift = torch.empty(cout, device=dev, dtype=_f32)
+    _lib.call("tmf_bn_eval_coeffs", gamma.data_ptr(), beta.data_ptr(), _ptr(bias), running_mean.data_ptr(),
+              running_var.data_ptr(), float(eps), cout, scale.data_ptr(), shift.data_ptr(), _stream())
+    return scale, shift
+
+
+def _bn_coeffs(training, part, rows, count, gamma, beta, bias, running_mean, running_var, momentum, eps, cout, dev):
+    """(mean, invstd, scale, shift) of a block's BatchNorm: in training from the `rows` statistic partials of the conv over
+    `count` voxels (and the running statistics move), in eval mode from the running statistics."""
+    if not training:
+        scale, shift = _bn_eval_coeffs(gamma, beta, bias, running_mean, running_var, eps, cout, dev)
+        # xhat = (z + bias - running_mean) * invstd, written as (z - mean) * invstd
+        invstd = torch.rsqrt(running_var + eps)
+        mean = running_mean - bias if bias is not None else running_mean.clone()
+        return mean, invstd, scale, shift
+    mean, invstd, scale, shift = (torch.empty(cout, device=dev, dtype=_f32) for _ in range(4))
+    _lib.call("tmf_bn_finalize", part.data_ptr(), rows, cout, count,
+              gamma.data_ptr(), beta.data_ptr(), _ptr(bias), _ptr(running_mean), _ptr(running_var),
+              float(momentum), float(eps), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), _stream())
+    return mean, invstd, scale, shift
+
+
+def _bn_bwd_tail(part, nblk, cout, count, training, has_bias, scale, dev):
+    """(dgamma, dbeta, coef, dbias) from the nblk partials of a backward-reduce pass; coef = (sum dy, sum dy xhat) / count."""
+    dgamma = torch.empty(cout, device=dev, dtype=_f32)
+    dbeta = torch.empty(cout, device=dev, dtype=_f32)
+    coef = torch.empty((2, cout), device=dev, dtype=_f32)
+    _lib.call("tmf_bn_bwd_finalize", part.data_ptr(), nblk, cout, count,
+              dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), _stream())
+    if training:
+        dbias = torch.zeros(cout, device=dev, dtype=_f32) if has_bias else None
     else:
-        nbytes = _lib.query("tmf_conv3d_wgrad_workspace_bytes", B, D, H, W, cin, cout, ksize)
-        ws = torch.empty((max(nbytes, 16) // 4,), device=x.device, dtype=_f32)
-        _lib.call("tmf_conv3d_wgrad", x.data_ptr(), dz.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes,
-                  B, D, H, W, cin, cout, ksize, int(reference_layout), _stream())
-    return dw
+        coef.zero_()                      # eval-mode BN is affine: dz = scale * dy
+        dbias = scale * dbeta if has_bias else None
+    return dgamma, dbeta, coef, dbias
 
 
 class ConvBnActPool(torch.autograd.Function):
@@ -334,56 +390,19 @@ class ConvBnActPool(torch.autograd.Function):
         weight = _chk(weight, "weight")
         # the kernel family per direction: the same choice as the whole-encoder path (snet_path.hip make_plan asks the same
         # query), so the two stay bit-identical
-        fam_f, fam_d, fam_w = ctx.fam = conv_block_algo(mode, cin, cout, k)
-        bf16 = {_lib.CONV_BF16: "bf16", _lib.CONV_SPLIT: "fp32x"}.get(fam_f, False)
-        z16 = bf16 == "bf16" and act16           # raw conv output (and dz) stored as bf16
-        if x.dtype == _b16 and bf16 != "bf16":
+        fam_f, fam_d, fam_w = ctx.fam = tuple(_CONV[a] for a in conv_block_algo(mode, cin, cout, k))
+        z16 = fam_f.io16 and act16               # raw conv output (and dz) stored as bf16
+        if x.dtype == _b16 and not fam_f.io16:
             x = x.float()                         # only the bf16 kernels read bf16 tensors
         if out_bf16 and not z16:
             raise _lib.TmfError("a bf16 block output needs conv precision 'bf16' with bf16 activation storage")
-        wf = wd = None
-        wino_f, wino_d = fam_f == _lib.CONV_WINO, fam_d == _lib.CONV_WINO       # (tmf_set_option("conv_wino", ..))
-        if not bf16:                      # both weight layouts in one launch; the dgrad one is kept for backward
-            want_d = ctx.needs_input_grad[0]
-            wf, wd = pack_weights_both(weight, want_d and not wino_d, want_fwd=not wino_f)
-            if wino_f or (wino_d and want_d):
-                uf, ud = pack_weights_wino(weight, wino_f, wino_d and want_d)
-                wf = uf if wino_f else wf
-                wd = ud if (wino_d and want_d) else wd
-        elif bf16 == "bf16":
-            wf, wd = pack_weights_both_bf16(weight, ctx.needs_input_grad[0] and fam_d == _lib.CONV_BF16)
-        else:                             # fp32x: both split layouts in one launch
-            wf, wd = pack_weights_split3(weight, ctx.needs_input_grad[0] and fam_d == _lib.CONV_SPLIT)
-
-        def conv(stats):
-            if bf16 == "bf16":
-                return conv3d_bf16_raw(x, wf, cin, cout, stats, out_bf16=z16)
-            if bf16 == "fp32x":
-                return conv3d_split_raw(x, wf, cin, cout, stats)
-            if wino_f:
-                return conv3d_wino_raw(x, wf, cin, cout, stats)
-            return conv3d_raw(x, wf, cin, cout, k, stats)
-
+        wf, wd = _pack_conv_weights(weight, fam_f, fam_d, ctx.needs_input_grad[0])      # the dgrad form is kept for backward
         dev = x.device
-        mean = torch.empty(cout, device=dev, dtype=_f32)
-        invstd = torch.empty(cout, device=dev, dtype=_f32)
-        scale = torch.empty(cout, device=dev, dtype=_f32)
-        shift = torch.empty(cout, device=dev, dtype=_f32)
         s = _stream()
         pc = _lib.pool_code(pool)
-        if training:
-            z, part, nblk = conv(True)
-            _lib.call("tmf_bn_finalize", part.data_ptr(), nblk, cout, float(B * D * H * W),
-                      gamma.data_ptr(), beta.data_ptr(), _ptr(bias), _ptr(running_mean), _ptr(running_var),
-                      float(momentum), float(eps), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                      shift.data_ptr(), s)
-        else:
-            z, _, _ = conv(False)
-            _lib.call("tmf_bn_eval_coeffs", gamma.data_ptr(), beta.data_ptr(), _ptr(bias), running_mean.data_ptr(),
-                      running_var.data_ptr(), float(eps), cout, scale.data_ptr(), shift.data_ptr(), s)
-            # xhat = (z + bias - running_mean) * invstd, written as (z - mean) * invstd
-            invstd = torch.rsqrt(running_var + eps)
-            mean = running_mean - bias if bias is not None else running_mean.clone()
+        z, part, nblk = _conv_forward(fam_f, x, wf, cin, cout, k, training, z16)
+        mean, invstd, scale, shift = _bn_coeffs(training, part, nblk, float(B * D * H * W), gamma, beta, bias,
+                                                running_mean, running_var, momentum, eps, cout, dev)
         odt = _b16 if out_bf16 else _f32
         if pc == _lib.POOL_NONE:
             out = torch.empty((B, D, H, W, cout), device=dev, dtype=odt)
@@ -414,39 +433,18 @@ class ConvBnActPool(torch.autograd.Function):
         part = torch.empty((nblk, 2, cout), device=dev, dtype=_f32)
         _lib.call("tmf_bn_act_pool_bwd_reduce_t", z.data_ptr(), dout.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                   mean.data_ptr(), invstd.data_ptr(), part.data_ptr(), B, D, H, W, cout, pc, slope, io, s)
-        dgamma = torch.empty(cout, device=dev, dtype=_f32)
-        dbeta = torch.empty(cout, device=dev, dtype=_f32)
-        coef = torch.empty((2, cout), device=dev, dtype=_f32)
-        _lib.call("tmf_bn_bwd_finalize", part.data_ptr(), nblk, cout, float(B * D * H * W),
-                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), s)
-        if training:
-            dbias = torch.zeros(cout, device=dev, dtype=_f32) if has_bias else None
-        else:
-            coef.zero_()                      # eval-mode BN is affine: dz = scale * dy
-            dbias = scale * dbeta if has_bias else None
+        dgamma, dbeta, coef, dbias = _bn_bwd_tail(part, nblk, cout, float(B * D * H * W), training, has_bias, scale, dev)
         dz = torch.empty_like(z)
         _lib.call("tmf_bn_act_pool_bwd_apply_t", z.data_ptr(), dout.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                   mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(), dz.data_ptr(), B, D, H, W, cout, pc, slope, io, s)
         _fam_f, fam_d, fam_w = ctx.fam
-        dweight = None
-        if ctx.needs_input_grad[1]:
-            if fam_w == _lib.CONV_BF16:
-                dweight = conv3d_wgrad_bf16(x, dz, cin, cout, reference_layout=True)
-            elif fam_w == _lib.CONV_WINO:
-                dweight = conv3d_wgrad_wino(x, dz, cin, cout, reference_layout=True)
-            else:
-                dweight = conv3d_wgrad(x, dz, cin, cout, k, reference_layout=True)
+        dweight = _conv_wgrad(fam_w, x, dz, cin, cout, k, True) if ctx.needs_input_grad[1] else None
         dx = None
         if ctx.needs_input_grad[0]:
-            if fam_d == _lib.CONV_BF16:
-                dx, _, _ = conv3d_bf16_raw(dz, weight, cout, cin, False, out_bf16=x.dtype == _b16)    # weight = packed wd
-            elif fam_d == _lib.CONV_SPLIT:
-                dx, _, _ = conv3d_split_raw(dz, weight, cout, cin, False)             # weight = packed split wd
-            elif fam_d == _lib.CONV_WINO:
-                dx, _, _ = conv3d_wino_raw(dz, weight, cout, cin, False)              # weight = packed Winograd u_dgrad
-            else:
-                dzf = dz if dz.dtype == _f32 else dz.float()
-                dx, _, _ = conv3d_raw(dzf, weight if ctx.packed_dgrad else pack_weight_dgrad(weight), cout, cin, k, False)
+            wd = weight if ctx.packed_dgrad else pack_weight_dgrad(weight)         # (saved: the dgrad form packed in forward, else the weight)
+            if dz.dtype != _f32 and not fam_d.io16:
+                dz = dz.float()                   # bf16 storage with a direct data gradient
+            dx, _, _ = _conv_forward(fam_d, dz, wd, cout, cin, k, False, fam_d.io16 and x.dtype == _b16)
             if dx.dtype != x.dtype:
                 dx = dx.to(x.dtype)
         return (dx, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None, None)
@@ -465,13 +463,9 @@ class Conv1BnPool(torch.autograd.Function):
         C = weight.shape[0]
         wp = pack_weight(_chk(weight, "weight")).view(27, C)
         dev = x.device
-        mean = torch.empty(C, device=dev, dtype=_f32)
-        invstd = torch.empty(C, device=dev, dtype=_f32)
-        scale = torch.empty(C, device=dev, dtype=_f32)
-        shift = torch.empty(C, device=dev, dtype=_f32)
         s = _stream()
         sfx = "_bf16" if mode == "bf16" else ""            # both products on the bf16 matrix cores (opt-in mode)
-        gram = None
+        gram = part = rows = None
         if training:
             nblk = _lib.query("tmf_c1_blocks", B, D, H, W, C)
             part = torch.empty((nblk, 2, C), device=dev, dtype=_f32)
@@ -483,15 +477,8 @@ class Conv1BnPool(torch.autograd.Function):
             else:                      # the recomputing pass (bf16: its own; fp32x keeps it: DESIGN 3.16)
                 _lib.call("tmf_c1_stats" + sfx, x.data_ptr(), wp.data_ptr(), part.data_ptr(), B, D, H, W, C, s)
                 rows = nblk
-            _lib.call("tmf_bn_finalize", part.data_ptr(), rows, C, float(B * D * H * W),
-                      gamma.data_ptr(), beta.data_ptr(), _ptr(bias), _ptr(running_mean), _ptr(running_var),
-                      float(momentum), float(eps), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                      shift.data_ptr(), s)
-        else:
-            _lib.call("tmf_bn_eval_coeffs", gamma.data_ptr(), beta.data_ptr(), _ptr(bias), running_mean.data_ptr(),
-                      running_var.data_ptr(), float(eps), C, scale.data_ptr(), shift.data_ptr(), s)
-            invstd = torch.rsqrt(running_var + eps)
-            mean = running_mean - bias if bias is not None else running_mean.clone()
+        mean, invstd, scale, shift = _bn_coeffs(training, part, rows, float(B * D * H * W), gamma, beta, bias,
+                                                running_mean, running_var, momentum, eps, C, dev)
         if out_bf16 and not sfx:
             raise _lib.TmfError("a bf16 block output needs conv precision 'bf16'")
         out = torch.empty((B, D // 2, H // 2, W // 2, C), device=dev, dtype=_b16 if out_bf16 else _f32)
@@ -551,16 +538,7 @@ class Conv1BnPool(torch.autograd.Function):
         part = torch.empty((nblk, 2, C), device=dev, dtype=_f32)
         _lib.call("tmf_c1_bwd_reduce" + sfx, x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                   mean.data_ptr(), invstd.data_ptr(), dout.data_ptr(), part.data_ptr(), B, D, H, W, C, slope, *p16, s)
-        dgamma = torch.empty(C, device=dev, dtype=_f32)
-        dbeta = torch.empty(C, device=dev, dtype=_f32)
-        coef = torch.empty((2, C), device=dev, dtype=_f32)
-        _lib.call("tmf_bn_bwd_finalize", part.data_ptr(), nblk, C, float(B * D * H * W),
-                  dgamma.data_ptr(), dbeta.data_ptr(), coef.data_ptr(), s)
-        if training:
-            dbias = torch.zeros(C, device=dev, dtype=_f32) if has_bias else None
-        else:
-            coef.zero_()
-            dbias = scale * dbeta if has_bias else None
+        dgamma, dbeta, coef, dbias = _bn_bwd_tail(part, nblk, C, float(B * D * H * W), training, has_bias, scale, dev)
         dweight = None
         if ctx.needs_input_grad[1]:
             nbytes = _lib.query("tmf_c1_bwd_wgrad_workspace_bytes", B, D, H, W, C)
@@ -581,22 +559,17 @@ def conv_bn_act_pool_eval_fused(x, weight, bias, gamma, beta, running_mean, runn
     if C != cin:
         raise _lib.TmfError(f"conv expects {cin} input channels, got {C}")
     dev = x.device
-    scale = torch.empty(cout, device=dev, dtype=_f32)
-    shift = torch.empty(cout, device=dev, dtype=_f32)
-    s = _stream()
-    _lib.call("tmf_bn_eval_coeffs", gamma.data_ptr(), beta.data_ptr(), _ptr(bias), running_mean.data_ptr(),
-              running_var.data_ptr(), float(eps), cout, scale.data_ptr(), shift.data_ptr(), s)
+    scale, shift = _bn_eval_coeffs(gamma, beta, bias, running_mean, running_var, eps, cout, dev)
     pc = _lib.pool_code(pool)
     shape = (B, D, H, W, cout) if pc == _lib.POOL_NONE else (B, D // 2, H // 2, W // 2, cout)
     out = torch.empty(shape, device=dev, dtype=_f32)
     if out.numel() > 0:
-        if conv_block_algo("fp32", cin, cout, k)[0] == _lib.CONV_WINO and pool != "avg":    # as tmf_snet_eval_fwd chooses
-            uf, _ = pack_weights_wino(weight, True, False)
-            _lib.call("tmf_conv3d_fwd_wino_affine", x.data_ptr(), uf.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                      out.data_ptr(), B, D, H, W, cin, cout, pc, float(slope), s)
-        else:
-            _lib.call("tmf_conv3d_fwd_affine", x.data_ptr(), pack_weight(weight).data_ptr(), scale.data_ptr(),
-                      shift.data_ptr(), out.data_ptr(), B, D, H, W, cin, cout, k, pc, float(slope), s)
+        fam = _CONV[conv_block_algo("fp32", cin, cout, k)[0]]
+        if pool == "avg":                                   # as tmf_snet_eval_fwd chooses: only the direct form averages
+            fam = _DIRECT
+        w = pack_weight(weight) if fam is _DIRECT else fam.pack(weight, True, False)[0]
+        _lib.call(fam.affine, x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(),
+                  B, D, H, W, *fam.fwd[1](cin, cout, k), pc, float(slope), _stream())
     return out
 
 
