@@ -1252,6 +1252,73 @@ int    tmf_rise_apply(const float* vol, const unsigned char* nodes, const int* s
 int    tmf_rise_accumulate(const float* scores, const unsigned char* nodes, const int* shifts, float* sal, float scale, int B,
                            int D, int H, int W, int sd, int sh, int sw, int N, int m_first, int m_step, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Atlas-region Shapley values (csrc/shap.hip; KernelSHAP, Lundberg & Lee 2017, in the paired-sampling form of Covert & Lee
+ * 2021): the players are the atlas regions of the volumes, a coalition keeps its members and replaces the other regions, and
+ * a least-squares fit under the efficiency constraint gives every player its share of score(scan) - score(all replaced).  The
+ * reference has no such function; these entries replace the loop its user writes with stock ops: a sampler, one torch.where
+ * per coalition and volume, and a dense solve.
+ *
+ * Players.  P players, 2 <= P <= TMF_SHAP_MAX_PLAYERS (= TMF_REGION_MAX).  A coalition is a bitset of Wd = ceil(P / 32) uint32
+ * words: player i is bit i & 31 of word i >> 5; the padding bits are 0 in every row, complements included.
+ * Coalition m.  Philox4x32-10 under the key (seed_lo ^ 0x53484150, seed_hi ^ 0x636F616C).  paired = 1: k = m >> 1 and an odd m
+ * is the complement of row m - 1 over the P players; paired = 0: k = m.
+ *   Size.  u = word 0 of counter (0, k, 1, 0); s = 1 + #{t in 0..P-3 : thr[t] <= u}, so 1 <= s <= P - 1.  thr is the table of
+ *     tmf_shap_size_table: w_r = 1.0 / ((double)r * (double)(P - r)) for r = 1..P-1, F_s = (w_1 + ... + w_s, added in
+ *     ascending r in fp64) / (the total, added the same way), thr[t] = min(2^32 - 1, floor(2^32 * F_{t+1})): the Shapley
+ *     kernel's distribution of sizes.  P = 2 has no thresholds and s = 1.
+ *   Members.  key_i = word i & 3 of counter (i >> 2, k, 0, 0).  Player i is in the coalition iff fewer than s players j have
+ *     (key_j, j) < (key_i, i) lexicographically: a uniform subset of size s, ties resolved by index.
+ *   Row m is a pure function of (seed, m, P, paired): independent of N, of m0 and of the call.
+ * Jobs.  Job j = b * N + m is sample b under row m of an [N][Wd] array (the caller may append rows of its own, an all-zero
+ * one for the empty coalition).  `labels` is an int32 volume [D][H][W] shared by the samples, as in tmf_occlude_labels; p0 is
+ * the first player of this volume, label l belongs to player p0 + l - 1.  Per voxel v with l = labels[v]:
+ *     out = vol[b][v]   if l <= 0, or l > R, or bit (p0 + l - 1) of the row is set;
+ *     out = f           otherwise, f = base[b][v] where a base is given, else fill[b].
+ * A pure select, the bits of torch.where.  Background is never replaced: the all-ones row gives the volume itself.
+ * Fit.  z_mi = bit i of row m, y[b][m] = (double)scores[b][m] - (double)offset[b].  A[i][j] = sum_m z_mi * z_mj in int32,
+ * exact.  rhs[b][i] = the sum of y[b][m] over the m with z_mi = 1, an fp64 chain in ascending m from 0.0.  No atomics: two
+ * calls give the same bits.
+ * Solve.  In fp64: M = A + ridge * I = L L^T (Cholesky), X = M^-1 [rhs_1 .. rhs_B, 1], and
+ *     phi_b = x_b - x_1 * (sum(x_b) - delta[b]) / sum(x_1),
+ * the minimiser of sum_m (y_m - sum_i z_mi phi_i)^2 subject to sum_i phi_i = delta[b].  info[0] = 0: solved; otherwise the
+ * 1-based index of the first pivot <= 0 (A is singular: too few coalitions for P) and every phi is NaN - not an error code.
+ * Two calls give the same bits.  Error: a Cholesky solve of M x = r has the relative forward error <= cond_2(M) * gamma with
+ * gamma ~ 3 P u to first order (u = 2^-53; Higham, Accuracy and Stability of Numerical Algorithms, Theorem 10.4 with
+ * || |L||L^T| || ~ ||M||).  phi takes two such solves (x_b and x_1): 6 P u; a reference solved in fp64 by another
+ * factorisation carries an error of the same size: 12 P u; rounded up to the next power of two,
+ *     |phi - phi_ref| <= 16 * P * 2^-53 * cond_2(M) * max|phi_ref|     per sample.
+ *
+ * tmf_shap_size_table: HOST array thr[max(P - 2, 0)] (thr may be NULL for P = 2).  No launch.
+ * tmf_shap_coalitions: coal [N][Wd], rows m0 .. m0+N-1; thr: the table in DEVICE memory (NULL allowed for P = 2).  ONE
+ *   launch; with `paired` an odd m0 or N is allowed.
+ * tmf_shap_apply: out [K][D][H][W] for jobs j0 .. j0+K-1 (coal holds rows 0 .. N-1); a chunk may straddle samples.  ONE
+ *   launch: a workgroup reads its voxels of vol, labels and base once per run of jobs of a sample and writes them once per job; 16 bytes
+ *   per lane where D*H*W % 4 == 0 and vol, out, labels (and base) are 16-byte aligned, one element per lane otherwise, with
+ *   equal bits on both paths.
+ * tmf_shap_gram: coal [N][Wd], scores [B][N], offset [B] -> A [P][P] int32 and rhs [B][P] fp64, EVERY element written.  Two
+ *   launches.
+ * tmf_shap_solve_workspace: the bytes tmf_shap_solve needs (0 for B or P outside their limits).
+ * tmf_shap_solve: A, rhs [B][P], delta [B] -> phi [B][P] fp64 and info[1], EVERY element written.  A fixed sequence of
+ *   launches (two per panel of 32 columns, three more), no cooperative grid.
+ * Refusals (negative code, nothing launched, the buffers untouched).  TMF_E_NULL: a null pointer, except fill where base is
+ * given, base where fill is given, and thr for P = 2.  TMF_E_SHAPE: P outside 2..TMF_SHAP_MAX_PLAYERS; an extent below 1 or
+ * D*H*W >= 2^31; B outside 1..65536; B*N >= 2^31.  TMF_E_ARG: paired not 0 / 1; N < 1, m0 < 0, m0 + N >= 2^31; R < 1, p0 < 0,
+ * p0 + R > P; K outside 1..65536, j0 < 0 or j0 + K > B*N; a ridge that is negative or not finite; out overlapping vol.
+ * TMF_E_ALIGN: a float, int32 or uint32 pointer that is not 4-byte aligned, a double pointer that is not 8-byte aligned, a
+ * workspace that is not 16-byte aligned.  TMF_E_WORKSPACE: fewer bytes than tmf_shap_solve_workspace(B, P). */
+#define TMF_SHAP_MAX_PLAYERS 1024     /* = TMF_REGION_MAX */
+int    tmf_shap_size_table(int P, unsigned* thr);
+int    tmf_shap_coalitions(unsigned* coal, const unsigned* thr, int P, int paired, unsigned long long seed, int m0, int N,
+                           void* stream);
+int    tmf_shap_apply(const float* vol, const int* labels, const unsigned* coal, const float* fill, const float* base, float* out,
+                      int B, int D, int H, int W, int R, int p0, int P, int N, int j0, int K, void* stream);
+int    tmf_shap_gram(const unsigned* coal, const float* scores, const float* offset, int* A, double* rhs, int B, int P, int N,
+                     void* stream);
+size_t tmf_shap_solve_workspace(int B, int P);
+int    tmf_shap_solve(const int* A, const double* rhs, const double* delta, double ridge, double* phi, int* info, void* workspace,
+                      size_t workspace_bytes, int B, int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

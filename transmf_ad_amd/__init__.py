@@ -26,6 +26,7 @@ from .region_stats import RegionAccumulator, RegionStats, region_stats, region_s
 from .clusters import Clusters, clusters, clusters_torch       # noqa: F401
 from .smooth import gaussian_smooth, gaussian_smooth_torch     # noqa: F401
 from .rise import Rise, rise, rise_torch                       # noqa: F401
+from .region_shap import RegionShap, region_shap, region_shap_torch   # noqa: F401
 from .networks import (Attention, CrossTransformer, CrossTransformer_MOD_AVG, FeedForward, PreNorm,   # noqa: F401
                        Transformer, sNet)
 
@@ -39,4 +40,4 @@ __all__ = ["model_ad", "model_CNN_ad", "model_single", "model_CNN", "model_trans
            "faithfulness_curve", "faithfulness_curve_torch",
            "region_stats", "region_stats_torch", "RegionStats", "RegionAccumulator",
            "clusters", "clusters_torch", "Clusters", "gaussian_smooth", "gaussian_smooth_torch",
-           "rise", "rise_torch", "Rise"]
+           "rise", "rise_torch", "Rise", "region_shap", "region_shap_torch", "RegionShap"]

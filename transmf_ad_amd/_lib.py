@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(_HERE, "libtmf_hip.so")
 _SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
             "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 _FIELD_SCALARS = dict(_SCALARS, int32_t=C.c_int32)
-_POINTEES = set(_FIELD_SCALARS) | {"void", "char", "unsigned char", "int64_t"}      # what a plain (void*) pointer may point to
+_POINTEES = set(_FIELD_SCALARS) | {"void", "char", "unsigned char", "unsigned", "int64_t"}      # what a plain (void*) pointer may point to
 _DEVICE_STRUCTS = {"tmf_augment_decision"}      # records in device memory: a pointer to one is a device pointer
 _TYPE_WORDS = {"const", "unsigned", "void", "char"} | set(_FIELD_SCALARS) | _POINTEES
 

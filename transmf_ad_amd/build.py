@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtmf_hip.so")
-SOURCES = ["options.hip", "conv3d_mfma.hip", "conv3d_wino.hip", "conv3d_winox.hip", "conv3d_bf16.hip", "conv1_fused.hip", "conv1_dgrad.hip", "conv1_gram.hip", "bn_act_pool.hip", "reduce.hip", "attention.hip", "token_ops.hip", "token_gemm.hip", "xformer_fused.hip", "snet_path.hip", "fusion_path.hip", "input_pipeline.hip", "heads.hip", "adam.hip", "sgd.hip", "losses.hip", "criterion.hip", "cam.hip", "occlusion.hip", "faithfulness.hip", "region_stats.hip", "clusters.hip", "smooth.hip", "rise.hip"]
+SOURCES = ["options.hip", "conv3d_mfma.hip", "conv3d_wino.hip", "conv3d_winox.hip", "conv3d_bf16.hip", "conv1_fused.hip", "conv1_dgrad.hip", "conv1_gram.hip", "bn_act_pool.hip", "reduce.hip", "attention.hip", "token_ops.hip", "token_gemm.hip", "xformer_fused.hip", "snet_path.hip", "fusion_path.hip", "input_pipeline.hip", "heads.hip", "adam.hip", "sgd.hip", "losses.hip", "criterion.hip", "cam.hip", "occlusion.hip", "faithfulness.hip", "region_stats.hip", "clusters.hip", "smooth.hip", "rise.hip", "shap.hip"]
 # -fno-slp-vectorize: clang's SLP pass pairs adjacent scalar fp32 adds / muls into v_pk_*_f32.  Beside MFMAs that is
 # slower on gfx950 (MI355X_MICROARCH.md: packed fp32 fillers cost +22..26 cycles per MFMA gap against scalar v_fma_f32) and
 # it makes the hot loops depend on the vectoriser's cost model of the day.  (Round 1 also blamed a run-to-run
@@ -22,7 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # `#pragma clang fp contract(off)`, so that file is compiled without contraction.
 # rise.hip: the mask value, the blend and the map are stated as chains of separately rounded operations (include/tmf_hip.h)
 # that a torch twin reproduces bit for bit, so it is compiled without contraction too.
-FILE_FLAGS = {"input_pipeline.hip": ["-ffp-contract=off"], "rise.hip": ["-ffp-contract=off"]}
+# shap.hip: the size table and the right-hand sides are stated as separately rounded fp64 chains; its solve kernels ask for
+# their fused multiply-adds by name.
+FILE_FLAGS = {"input_pipeline.hip": ["-ffp-contract=off"], "rise.hip": ["-ffp-contract=off"], "shap.hip": ["-ffp-contract=off"]}
 # extra compile flags for one-off instrumented builds (e.g. TMF_EXTRA_FLAGS=-DTMF_ABLATE for tools/bf16_ablate.py); part
 # of the stamp, so such a library is only loaded by processes started with the same setting
 FLAGS += os.environ.get("TMF_EXTRA_FLAGS", "").split()

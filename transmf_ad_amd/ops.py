@@ -1712,6 +1712,251 @@ def rise_accumulate(scores, nodes, shifts, size, cells, scale=1.0, m_first=0, m_
 
 
 # --------------------------------------------------------------------------------------
+# atlas-region Shapley values (csrc/shap.hip; include/tmf_hip.h states the players, the coalitions, the jobs, the fit and the solve)
+# --------------------------------------------------------------------------------------
+
+SHAP_KEY = (0x53484150, 0x636F616C)      # XORed into the two halves of the seed
+SHAP_MAX_PLAYERS = _lib.SHAP_MAX_PLAYERS
+
+
+def shap_ok(*tensors):
+    """The Shapley kernels take these: contiguous float32 (int32 labels, coalitions and A, float64 rhs and delta) tensors on one
+    HIP device, none empty."""
+    return _kernel_takes(*((t, (_f32, torch.int32, torch.float64)) for t in tensors))
+
+
+def _shap_players(P):
+    return _int(P, f"P must be an integer in 2..{SHAP_MAX_PLAYERS} players", 2, SHAP_MAX_PLAYERS)
+
+
+def shap_size_table_torch(P):
+    """thr (max(P - 2, 0),) int64 with values in 0..2^32-1, restated in numpy: w_r = 1 / (r (P - r)), F_s the ascending fp64
+    partial sum over the ascending total, thr[t] = min(2^32 - 1, floor(2^32 F_{t+1}))."""
+    import numpy as np
+    P = _shap_players(P)
+    total = part = np.float64(0.0)
+    for r in range(1, P):
+        total = total + np.float64(1.0) / (np.float64(r) * np.float64(P - r))
+    thr = np.empty(max(P - 2, 0), np.int64)
+    for t in range(P - 2):
+        part = part + np.float64(1.0) / (np.float64(t + 1) * np.float64(P - t - 1))
+        thr[t] = min(2 ** 32 - 1, int(np.floor(np.float64(4294967296.0) * (part / total))))
+    return torch.from_numpy(thr)
+
+
+def shap_size_table(P):
+    """thr (max(P - 2, 0),) int64 with values in 0..2^32-1 from the library's host entry tmf_shap_size_table."""
+    P = _shap_players(P)
+    thr = (ctypes.c_uint32 * max(P - 2, 1))()
+    _lib.call("tmf_shap_size_table", P, thr)
+    return torch.tensor(list(thr)[:P - 2], dtype=torch.int64)
+
+
+def _shap_coalition_args(P, paired, seed, m0, N):
+    _shap_players(P)
+    if not _is_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
+    if not (_is_int(m0) and _is_int(N) and N >= 1 and m0 >= 0 and m0 + N < 1 << 31):
+        raise ValueError(f"coalitions m0 = {m0!r}, N = {N!r}")
+    return (P + 31) // 32
+
+
+def _shap_bits32(words):
+    """uint32 values held in an int64 tensor / array -> the int32 tensor with the same bits."""
+    import numpy as np
+    return torch.from_numpy(np.asarray(words, dtype=np.int64).astype(np.uint32).view(np.int32))
+
+
+def _shap_coalitions_host(P, paired, seed, m0, N):
+    """The rows as the header defines them, in numpy on the host -> (N, Wd) int32 (the bits of the uint32 words)."""
+    import numpy as np
+    u64, mask32 = np.uint64, np.uint64(0xFFFFFFFF)
+
+    def philox(c0, c1, c2, c3):
+        c0, c1, c2, c3 = (np.asarray(c, dtype=u64) for c in np.broadcast_arrays(c0, c1, c2, c3))
+        k0, k1 = u64((seed & 0xFFFFFFFF) ^ SHAP_KEY[0]), u64((seed >> 32) ^ SHAP_KEY[1])
+        for _ in range(10):
+            p0, p1 = u64(0xD2511F53) * c0, u64(0xCD9E8D57) * c2
+            c0, c1, c2, c3 = (p1 >> u64(32)) ^ c1 ^ k0, p1 & mask32, (p0 >> u64(32)) ^ c3 ^ k1, p0 & mask32
+            k0, k1 = (k0 + u64(0x9E3779B9)) & mask32, (k1 + u64(0xBB67AE85)) & mask32
+        return np.stack([c0, c1, c2, c3], -1)
+
+    Wd = (P + 31) // 32
+    m = np.arange(m0, m0 + N)
+    k = m >> 1 if paired else m
+    ks = np.arange(k[0], k[-1] + 1, dtype=u64)
+    u = philox(0, ks, 1, 0)[:, 0]
+    s = 1 + np.searchsorted(shap_size_table_torch(P).numpy().astype(u64), u, side="right")     # #{t : thr[t] <= u}
+    nq = (P + 3) // 4
+    keys = philox(np.arange(nq, dtype=u64)[None, :], ks[:, None], 0, 0).reshape(len(ks), nq * 4)[:, :P]
+    order = np.argsort(keys, axis=1, kind="stable")                                              # ties by index
+    rank = np.empty_like(order)
+    np.put_along_axis(rank, order, np.broadcast_to(np.arange(P), order.shape), 1)
+    z = (rank < s[:, None])[k - k[0]]
+    if paired:
+        z = np.where((m & 1)[:, None] == 1, ~z, z)
+    bits = np.zeros((N, Wd * 32), np.int64)
+    bits[:, :P] = z
+    words = (bits.reshape(N, Wd, 32) << np.arange(32, dtype=np.int64)).sum(2)
+    return _shap_bits32(words)
+
+
+def shap_coalitions_torch(P, paired, seed, m0, N, device=None):
+    """shap_coalitions restated in numpy on the host (Philox4x32-10, the size table, ranks by a stable sort), then moved to
+    `device`: the same bits as the kernel's."""
+    _shap_coalition_args(P, paired, seed, m0, N)
+    return _shap_coalitions_host(P, bool(paired), seed, m0, N).to(torch.device("cpu" if device is None else device))
+
+
+def shap_coalitions(P, paired, seed, m0, N, device):
+    """(N, Wd) int32, the bits of rows m0 .. m0+N-1 of the coalition sampler: player i is bit i & 31 of word i >> 5.  A pure
+    function of (seed, m, P, paired).  A HIP device: ONE launch (tmf_shap_coalitions); anything else: shap_coalitions_torch."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return shap_coalitions_torch(P, paired, seed, m0, N, device)
+    Wd = _shap_coalition_args(P, paired, seed, m0, N)
+    with torch.cuda.device(device):
+        thr = _shap_bits32(shap_size_table(P).numpy()).to(device) if P > 2 else None
+        coal = torch.empty((N, Wd), device=device, dtype=torch.int32)
+        _lib.call("tmf_shap_coalitions", coal.data_ptr(), _ptr(thr), P, 1 if paired else 0, seed, m0, N, _stream())
+    return coal
+
+
+def shap_unpack(coal, P):
+    """(N, Wd) int32 rows -> (N, P) bool: z[m, i] = player i is in coalition m."""
+    i = torch.arange(P, device=coal.device)
+    return ((coal.long()[:, i >> 5] >> (i & 31)) & 1).bool()
+
+
+def _shap_apply_args(vol, labels, coal, fill, R, p0, P, j0, K, base, out):
+    B, size = vol.shape[0], tuple(vol.shape[-3:])
+    _shap_players(P)
+    if tuple(labels.shape) != size or labels.dtype.is_floating_point:
+        raise ValueError(f"labels must be integers of shape {size}, got {tuple(labels.shape)} {labels.dtype}")
+    if not (_is_int(R) and _is_int(p0) and R >= 1 and p0 >= 0 and p0 + R <= P):
+        raise ValueError(f"players p0 = {p0!r}, R = {R!r} of {P}")
+    if coal.dim() != 2 or coal.dtype != torch.int32 or coal.shape[0] < 1 or coal.shape[1] != (P + 31) // 32:
+        raise ValueError(f"coalitions must be (N, {(P + 31) // 32}) int32, got {tuple(coal.shape)} {coal.dtype}")
+    N = coal.shape[0]
+    _job_range(B, N, j0, K)
+    out = _job_buffer(vol, K, out)
+    if base is None and (fill is None or tuple(fill.shape) != (B,)):
+        raise ValueError(f"fill must be ({B},), got {None if fill is None else tuple(fill.shape)}")
+    if base is not None and tuple(base.shape) != tuple(vol.shape):
+        raise ValueError(f"base must be {tuple(vol.shape)}, got {tuple(base.shape)}")
+    return out, N
+
+
+def _shap_apply_rows(vol, labels, coal, fill, R, p0, N, j0, K, base, out):
+    lab = labels.to(vol.device).long()
+    coal = coal.to(vol.device).long()
+    has = (lab >= 1) & (lab <= R)
+    player = torch.where(has, p0 + lab - 1, torch.zeros_like(lab))
+    word, bit = player >> 5, player & 31
+    for k in range(K):
+        b, m = divmod(j0 + k, N)
+        keep = ~has | ((coal[m][word] >> bit) & 1).bool()
+        out[k] = torch.where(keep, vol[b], base[b] if base is not None else fill[b])
+    return out
+
+
+def shap_apply_torch(vol, labels, coal, fill, R, p0, P, j0, K, base=None, out=None):
+    """shap_apply in plain torch ops on whatever device and dtype vol has: one torch.where per job."""
+    out, N = _shap_apply_args(vol, labels, coal, fill, R, p0, P, j0, K, base, out)
+    return _shap_apply_rows(vol, labels, coal, fill, R, p0, N, j0, K, base, out)
+
+
+def shap_apply(vol, labels, coal, fill, R, p0, P, j0, K, base=None, out=None):
+    """out[k] = sample b of vol (B, ..., D, H, W) under coalition row m of coal (N, Wd), job j0 + k = b*N + m: a voxel with
+    label l in 1..R keeps its value where bit p0 + l - 1 of the row is set and takes base[b] (where given, else fill[b])
+    otherwise; background and labels outside 1..R are never replaced -> (K, ..., D, H, W).  Contiguous float32 HIP tensors
+    (int32 labels and coalitions): ONE launch (tmf_shap_apply); anything else: shap_apply_torch, the same bits."""
+    out, N = _shap_apply_args(vol, labels, coal, fill, R, p0, P, j0, K, base, out)
+    B = vol.shape[0]
+    if not (shap_ok(vol, labels, coal, base if base is not None else fill, out) and vol.dtype == _f32 and out.dtype == _f32
+            and labels.dtype == torch.int32 and (base if base is not None else fill).dtype == _f32
+            and vol.numel() == B * labels.numel()):
+        return _shap_apply_rows(vol, labels, coal, fill, R, p0, N, j0, K, base, out)
+    _chk(vol, "vol")
+    _lib.call("tmf_shap_apply", vol.data_ptr(), labels.data_ptr(), coal.data_ptr(), _ptr(None if base is not None else fill),
+              _ptr(base), out.data_ptr(), B, *labels.shape, R, p0, P, N, j0, K, _stream())
+    return out
+
+
+def _shap_gram_args(coal, scores, offset, P):
+    _shap_players(P)
+    if coal.dim() != 2 or coal.dtype != torch.int32 or coal.shape[0] < 1 or coal.shape[1] != (P + 31) // 32:
+        raise ValueError(f"coalitions must be (N, {(P + 31) // 32}) int32, got {tuple(coal.shape)} {coal.dtype}")
+    N = coal.shape[0]
+    if scores.dim() != 2 or scores.shape[1] != N or scores.shape[0] < 1 or tuple(offset.shape) != (scores.shape[0],):
+        raise ValueError(f"scores must be (B, {N}) and offset (B,), got {tuple(scores.shape)} and {tuple(offset.shape)}")
+    return scores.shape[0], N
+
+
+def shap_gram_torch(coal, scores, offset, P):
+    """shap_gram in plain torch ops on whatever device the scores have: the unpacked bits, two fp64 matrix products (A is exact:
+    its entries are counts below 2^31)."""
+    _shap_gram_args(coal, scores, offset, P)
+    z = shap_unpack(coal.to(scores.device), P).double()
+    y = scores.double() - offset.double().view(-1, 1)
+    return (z.t() @ z).to(torch.int32), y @ z
+
+
+def shap_gram(coal, scores, offset, P):
+    """The normal equations of the fit: coal (N, Wd), scores (B, N), offset (B,) -> (A (P, P) int32 = sum_m z_m z_m^T, exact;
+    rhs (B, P) float64 = sum_m z_mi (scores[b, m] - offset[b]), an ascending chain).  Contiguous float32 HIP scores: two
+    launches (tmf_shap_gram), no atomics; anything else: shap_gram_torch."""
+    B, N = _shap_gram_args(coal, scores, offset, P)
+    if not (shap_ok(coal, scores, offset) and scores.dtype == _f32 and offset.dtype == _f32):
+        return shap_gram_torch(coal, scores, offset, P)
+    A = torch.empty((P, P), device=scores.device, dtype=torch.int32)
+    rhs = torch.empty((B, P), device=scores.device, dtype=torch.float64)
+    _lib.call("tmf_shap_gram", coal.data_ptr(), scores.data_ptr(), offset.data_ptr(), A.data_ptr(), rhs.data_ptr(), B, P, N, _stream())
+    return A, rhs
+
+
+def _shap_solve_args(A, rhs, delta, ridge):
+    P = A.shape[-1]
+    _shap_players(P)
+    if tuple(A.shape) != (P, P) or A.dtype.is_floating_point or rhs.dim() != 2 or rhs.shape[1] != P or rhs.shape[0] < 1 \
+            or tuple(delta.shape) != (rhs.shape[0],):
+        raise ValueError(f"A must be integers ({P}, {P}), rhs (B, {P}) and delta (B,), got {tuple(A.shape)}, {tuple(rhs.shape)} "
+                         f"and {tuple(delta.shape)}")
+    if not isinstance(ridge, (int, float)) or isinstance(ridge, bool) or not (0.0 <= float(ridge) < math.inf):
+        raise ValueError(f"ridge must be a finite number >= 0, got {ridge!r}")
+    return rhs.shape[0], P
+
+
+def shap_solve_torch(A, rhs, delta, ridge=0.0):
+    """shap_solve with torch.linalg in float64 on whatever device A has: cholesky_ex, cholesky_solve, the closed form."""
+    _B, P = _shap_solve_args(A, rhs, delta, ridge)
+    M = A.double() + float(ridge) * torch.eye(P, device=A.device, dtype=torch.float64)
+    L, info = torch.linalg.cholesky_ex(M)
+    X = torch.cholesky_solve(torch.cat([rhs.double(), torch.ones((1, P), device=A.device, dtype=torch.float64)]).t(), L).t()
+    xb, x1 = X[:-1], X[-1]
+    phi = xb - x1 * ((xb.sum(1) - delta.double()) / x1.sum()).view(-1, 1)
+    info = info.to(torch.int32).view(1)
+    return torch.where(info == 0, phi, torch.full_like(phi, math.nan)), info
+
+
+def shap_solve(A, rhs, delta, ridge=0.0):
+    """The fit under the efficiency constraint: with M = A + ridge I, X = M^-1 [rhs_1 .. rhs_B, 1],
+    phi_b = x_b - x_1 (sum x_b - delta_b) / sum x_1 -> (phi (B, P) float64, info (1,) int32: 0, or the 1-based index of the first
+    pivot <= 0 of the Cholesky factorisation - A is singular - and phi all NaN).  Contiguous HIP tensors (int32 A, float64 rhs
+    and delta): a fixed sequence of launches (tmf_shap_solve), no host read; anything else: shap_solve_torch."""
+    B, P = _shap_solve_args(A, rhs, delta, ridge)
+    if not (_kernel_takes((A, torch.int32), (rhs, torch.float64), (delta, torch.float64))):
+        return shap_solve_torch(A, rhs, delta, ridge)
+    nbytes = _lib.query("tmf_shap_solve_workspace", B, P)
+    ws = torch.empty((nbytes,), device=A.device, dtype=torch.uint8)
+    phi = torch.empty((B, P), device=A.device, dtype=torch.float64)
+    info = torch.empty((1,), device=A.device, dtype=torch.int32)
+    _lib.call("tmf_shap_solve", A.data_ptr(), rhs.data_ptr(), delta.data_ptr(), float(ridge), phi.data_ptr(), info.data_ptr(),
+              ws.data_ptr(), nbytes, B, P, _stream())
+    return phi, info
+
+
+# --------------------------------------------------------------------------------------
 # deletion / insertion curves (csrc/faithfulness.hip; include/tmf_hip.h states the ordering, the thresholds and the jobs)
 # --------------------------------------------------------------------------------------
 
